@@ -11,6 +11,11 @@ scaling, no data-path collective); value = txs of all ranks / max-over-ranks wal
 --steps steps are timed; the warm-up runs at least --warmup steps AND --warm-seconds of back-to-back
 launches so the clock has settled under load before the timed region starts.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does that and nothing else: it sets up, warms up,
+times the K steps, writes the outputs of the last timed step when --dump-outputs DIR is given (float32
+.npy files; the inputs are seeded, so two builds run with the same arguments can be compared output for
+output) and prints the line.  Everything below runs only with --full, after the headline leg.
+
 Sub-legs in the same line (`legs`), each timed for >= --leg-seconds of back-to-back steps:
   c2sm2  C2's size on the guomi suite: 10k SM2/SM3 txs per GPU (the SM2 pair kernel; weak scaling).
   c3  configs[2]: 1M SM2/SM3 txs per GPU: SM3 tx hash + SM2 verify + sender (weak scaling).
@@ -425,8 +430,39 @@ def run_leg(ctx, wl_name, steps=None, warmup=3, warm_seconds=0.0, min_seconds=2.
     rec = {"workload": wl["name"], "value": units_total * steps / elapsed, "unit": "tx/s",
            "ms_per_step": elapsed / steps * 1e3, "steps": steps, "timed_s": elapsed, "scaling": wl["scaling"],
            "txs_total": units_total, "txs_rank0": n, "valid_frac": ok_frac, "roofline": roofline}
-    state = {"batch": b, "status": status[:n], "n": n}
+    # what a caller of the timed step receives, as the last timed step left it (--dump-outputs)
+    outputs = {"txhash": txhash[:n], "sender": sender[:n], "status": status[:n]}
+    if txroot is not None:
+        outputs["tx_root"] = txroot.root
+    elif block_off is not None and n:
+        outputs["block_roots"] = roots
+    state = {"batch": b, "status": status[:n], "n": n, "outputs": outputs}
     return rec, state
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: each output array of the headline leg's last timed step as out_dir/<name>.npy
+    in float32 (byte values are exact in it), DUMP_MAX_BYTES in all.  Where the arrays are larger, the
+    per-tx ones (same leading length) keep the same seeded sample of rows, in row order, so two builds
+    run with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.size * 4 for a in arrays.values())
+    rows = max(a.shape[0] for a in arrays.values())
+    keep = None
+    if total > DUMP_MAX_BYTES:
+        per_row = sum(a.size // rows * 4 for a in arrays.values() if a.shape[0] == rows)
+        fixed = total - per_row * rows
+        k = max((DUMP_MAX_BYTES - fixed) // per_row, 1)
+        keep = np.sort(np.random.default_rng(0xD0).choice(rows, size=k, replace=False))
+    for name, a in arrays.items():
+        if keep is not None and a.shape[0] == rows:
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 MERKLE_SPECS = [(n, hname, width) for n in (100_000, 1_000_000, 16_000_000)
@@ -1263,7 +1299,8 @@ def dumps_line(line):
     return json.dumps(line, allow_nan=False, separators=(",", ":"))
 
 
-def main():
+def parse_args(argv=None):
+    """The command line; without --full every leg but the headline is switched off."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4500, help="timed steps of the headline (C2) leg")
@@ -1277,15 +1314,33 @@ def main():
     ap.add_argument("--devset", default="auto",
                     help="device list for the one-process device-set legs (C4/C5 through bcosgpu_block_verify_multi): "
                          "'auto' = every rank's GPU when N > 1, {0, 0} at N = 1; 'none' to skip; or e.g. '0,1'")
-    ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="where rank 0 writes the full record (every leg, notes, nested objects)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also run everything else: the sub-legs (--legs), the device-set "
+                         "legs (--devset), the PCIe, createTransaction, interface and sealer-verify legs, the "
+                         "hashes/s and Merkle legs and the CPU baselines (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes the headline leg's outputs of its last timed step "
+                         "(txhash, sender, status; tx_root / block_roots for c4 / c5) as DIR/<name>.npy, float32")
+    ap.add_argument("--detail-out", default=None,
+                    help="where rank 0 writes the full record (every leg, notes, nested objects); by default "
+                         "bench_out/bench_detail.json with --full and nowhere without it ('' for nowhere)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-merkle", action="store_true")
     ap.add_argument("--no-hashes", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the PCIe and createTransaction legs")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU test of the --gpus launcher path only: spawn, rendezvous (gloo), max over ranks; no GPU work")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.detail_out is None:
+        args.detail_out = os.path.join("bench_out", "bench_detail.json") if args.full else ""
+    if not args.full:  # the plain run: set up, warm up, time the headline's steps, print the line
+        args.legs, args.devset = "", "none"
+        args.no_extras = args.no_hashes = args.no_merkle = args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    args = parse_args()
     global EVENT_EVERY
     EVENT_EVERY = max(1, args.event_every)
 
@@ -1328,6 +1383,8 @@ def main():
 
     head, head_state = run_leg(ctx, args.workload, steps=args.steps, warmup=args.warmup,
                                warm_seconds=args.warm_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(head_state.pop("outputs"), args.dump_outputs)
     legs = {}
     states = {}
     for wl in [x for x in args.legs.split(",") if x and x != args.workload]:

@@ -110,6 +110,53 @@ def test_line_survives_failed_extra_legs():
     assert len(text) < bench.LINE_MAX
 
 
+def test_plain_run_is_the_headline_alone_and_full_keeps_every_leg():
+    """Without --full every leg but the headline is off and no detail file is written; --full leaves the
+    legs' own switches as given."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--legs", "c3", "--devset", "0,0"])
+    assert (a.steps, a.warmup, a.legs, a.devset, a.detail_out, a.dump_outputs) == (7, 2, "", "none", "", None)
+    assert a.no_extras and a.no_hashes and a.no_merkle and a.no_cpu_baseline
+    f = bench.parse_args(["--full", "--no-merkle", "--dump-outputs", "d"])
+    assert f.legs == "c2sm2,c3,c4,c5" and f.devset == "auto" and f.detail_out.endswith("bench_detail.json")
+    assert f.no_merkle and not (f.no_extras or f.no_hashes or f.no_cpu_baseline) and f.dump_outputs == "d"
+    assert bench.parse_args(["--full", "--detail-out", ""]).detail_out == ""
+    assert bench.parse_args(["--detail-out", "x.json"]).detail_out == "x.json"
+
+
+def test_dump_outputs_float32_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every output as <name>.npy in float32 with the exact byte values; past the size
+    limit the per-tx arrays keep one seeded sample of rows (the same rows in each, the same on every
+    run) and the whole dump stays under the limit."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(5)
+    n = 1000
+    outs = {"txhash": torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)),
+            "sender": torch.from_numpy(rng.integers(0, 256, (n, 20), dtype=np.uint8)),
+            "status": torch.from_numpy(rng.integers(0, 2, n, dtype=np.uint8)),
+            "tx_root": torch.from_numpy(rng.integers(0, 256, 32, dtype=np.uint8))}
+    bench.dump_outputs(outs, str(tmp_path / "all"))
+    for k, v in outs.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy().astype(np.float32)), k
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40_000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(outs, str(tmp_path / d))
+    got = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in outs}
+    assert sum(a.nbytes for a in got.values()) <= 40_000
+    rows = got["status"].shape[0]
+    assert 100 < rows < n and got["txhash"].shape == (rows, 32) and got["sender"].shape == (rows, 20)
+    assert np.array_equal(got["tx_root"], outs["tx_root"].numpy().astype(np.float32))
+    # the same rows of every per-tx array, in row order: find them through the (distinct) hashes
+    th = outs["txhash"].numpy()
+    idx = [int(np.nonzero((th == r).all(axis=1))[0][0]) for r in got["txhash"].astype(np.uint8)]
+    assert idx == sorted(set(idx))
+    assert np.array_equal(got["sender"], outs["sender"].numpy()[idx].astype(np.float32))
+    assert np.array_equal(got["status"], outs["status"].numpy()[idx].astype(np.float32))
+    for k in outs:
+        assert np.array_equal(got[k], np.load(tmp_path / "s2" / (k + ".npy"))), k
+
+
 def test_safe_returns_error_record(capsys):
     assert bench._safe("x", lambda: {"ok": 1}) == {"ok": 1}
     r = bench._safe("x", lambda: 1 / 0)
