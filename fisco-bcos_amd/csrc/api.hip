@@ -1,6 +1,7 @@
 // api.hip -- the C ABI (include/bcos_gpu.h): argument checks, per-device workspaces for the
 // host-pointer entry points, and the wedpr-shaped single-call shims.  No exceptions cross the ABI.
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -16,48 +17,12 @@ int set_err(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-int hip_err(hipError_t e, const char* what) {
-    return set_err(BCOSGPU_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
+int hip_err(hipError_t e, const char* what) { return set_err(BCOSGPU_E_HIP, hip_msg(e, what)); }
 #define HIP_OK(call)                                   \
     do {                                               \
         hipError_t e_ = (call);                        \
         if (e_ != hipSuccess) return hip_err(e_, #call); \
     } while (0)
-
-// Grow-only device buffer.
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-// Grow-only pinned host buffer (staging for packers that write straight into DMA-able memory).
-struct HostBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes < 65536 ? 65536 : bytes + bytes / 4;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
 
 // One workspace per device for the synchronous host-pointer API; the mutex makes those entry
 // points safe to call from the reference's concurrent verifier pools (TxPool.h:48-49).
@@ -66,7 +31,7 @@ struct Workspace {
     bool ready = false;
     hipStream_t stream = nullptr;
     DevBuf b[8];
-    HostBuf h[2];
+    PinnedBuf h[2];  // staging for packers that write straight into DMA-able memory
 };
 std::mutex g_mu;
 std::vector<Workspace*> g_ws;
@@ -93,6 +58,40 @@ int get_ws(Workspace** out) {
     return 0;
 }
 
+// One call on the workspace of the calling thread's device.  It owns, in this order, the workspace, its
+// lock and the drain of its stream: whatever way the call returns before finish(), the stream is idle
+// before the mutex is released, so nothing of a failed call writes the caller's memory or runs into the
+// next call's buffers.  `if (c.rc) return c.rc;` follows the declaration.
+struct WsCall {
+    Workspace* w = nullptr;
+    const int rc;
+    std::unique_lock<std::mutex> lock;
+    StreamDrain drain;
+    WsCall()
+        : rc(get_ws(&w)), lock(rc ? std::unique_lock<std::mutex>() : std::unique_lock<std::mutex>(w->mu)),
+          drain(rc ? nullptr : w->stream) {}
+    hipStream_t stream() const { return w->stream; }
+    template <class T = uint8_t> T* buf(int i) const { return w->b[i].as<T>(); }
+    // buffers 0, 1, ... of at least these sizes (0: not used by this call)
+    hipError_t ensure(std::initializer_list<size_t> bytes) {
+        int i = 0;
+        for (size_t n : bytes)
+            if (hipError_t e = w->b[i++].ensure(n)) return e;
+        return hipSuccess;
+    }
+    hipError_t h2d(int i, const void* src, size_t bytes) {
+        return hipMemcpyAsync(w->b[i].p, src, bytes, hipMemcpyHostToDevice, w->stream);
+    }
+    hipError_t d2h(void* dst, int i, size_t bytes) {
+        return hipMemcpyAsync(dst, w->b[i].p, bytes, hipMemcpyDeviceToHost, w->stream);
+    }
+    int finish() {  // the synchronisation that ends the success path
+        HIP_OK(hipStreamSynchronize(w->stream));
+        drain.dismiss();
+        return 0;
+    }
+};
+
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
 
 int init_device(int device, int flags);
@@ -101,14 +100,8 @@ int init_device(int device, int flags);
 // current device.
 int ready_device(int device) {
     if (device >= 0 && device < 64 && g_ready[device].load(std::memory_order_acquire)) return 0;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) {
-        (void)hipGetLastError();
-        prev = -1;
-    }
-    const int rc = init_device(device, 0);
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    return rc;
+    DeviceScope keep(device);  // (init_device selects the device itself and reports why it could not)
+    return init_device(device, 0);
 }
 
 // A host-pointer signature call as a coalesced job (coalesce.hip) on `device`.
@@ -195,7 +188,7 @@ int bcosgpu_set_tx_kernel_policy(int split, int occupancy, int coop, int field) 
 // ------------------------------------------------------------------ hashing
 int bcosgpu_hash_batch_dev(int hasher, const uint8_t* d_data, const uint64_t* d_offsets, size_t n,
                            uint8_t* d_out32, void* stream) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (n && (!d_data || !d_offsets || !d_out32)) return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_hash_batch(hasher, d_data, d_offsets, n, d_out32, as_stream(stream));
     return rc ? hip_err(hipGetLastError(), "hash_batch launch") : 0;
@@ -203,29 +196,24 @@ int bcosgpu_hash_batch_dev(int hasher, const uint8_t* d_data, const uint64_t* d_
 
 int bcosgpu_hash_batch(int hasher, const uint8_t* data, const uint64_t* offsets, size_t n,
                        uint8_t* out32) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (n == 0) return 0;
     if (!data || !offsets || !out32) return set_err(BCOSGPU_E_ARG, "null pointer");
     const uint64_t base = offsets[0], bytes = offsets[n] - base;
     for (size_t i = 0; i < n; ++i)
         if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFFFull)
             return set_err(BCOSGPU_E_ARG, "offsets must be non-decreasing and messages < 4 GiB");
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
-    HIP_OK(w->b[0].ensure(bytes + 8));
-    HIP_OK(w->b[1].ensure((n + 1) * 8));
-    HIP_OK(w->b[2].ensure(n * 32));
-    std::vector<uint64_t> off(n + 1);
+    std::vector<uint64_t> off(n + 1);  // (declared before the call: the drain runs while it is alive)
     for (size_t i = 0; i <= n; ++i) off[i] = offsets[i] - base;
-    HIP_OK(hipMemcpyAsync(w->b[0].p, data + base, bytes, hipMemcpyHostToDevice, w->stream));
-    HIP_OK(hipMemcpyAsync(w->b[1].p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, w->stream));
-    rc = launch_hash_batch(hasher, w->b[0].as<uint8_t>(), w->b[1].as<uint64_t>(), n, w->b[2].as<uint8_t>(), w->stream);
-    if (rc) return hip_err(hipGetLastError(), "hash_batch launch");
-    HIP_OK(hipMemcpyAsync(out32, w->b[2].p, n * 32, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    WsCall c;
+    if (c.rc) return c.rc;
+    HIP_OK(c.ensure({bytes + 8, (n + 1) * 8, n * 32}));
+    HIP_OK(c.h2d(0, data + base, bytes));
+    HIP_OK(c.h2d(1, off.data(), (n + 1) * 8));
+    if (launch_hash_batch(hasher, c.buf(0), c.buf<uint64_t>(1), n, c.buf(2), c.stream()))
+        return hip_err(hipGetLastError(), "hash_batch launch");
+    HIP_OK(c.d2h(out32, 2, n * 32));
+    return c.finish();
 }
 
 int bcosgpu_keccak256_batch(const uint8_t* data, const uint64_t* offsets, size_t n, uint8_t* out32) {
@@ -238,9 +226,9 @@ int bcosgpu_sm3_batch(const uint8_t* data, const uint64_t* offsets, size_t n, ui
 // ------------------------------------------------------------------ Merkle
 int bcosgpu_merkle_root_dev(int hasher, int width, const uint8_t* d_leaves32, size_t n,
                             uint8_t* d_tree, uint8_t* d_root32, void* stream) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (n == 0) return set_err(BCOSGPU_E_EMPTY, "Empty input");
-    if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_width(width)) return rc;
     if (!d_leaves32 || !d_tree) return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_merkle(hasher, width, d_leaves32, n, d_tree, d_root32, as_stream(stream));
     return rc ? hip_err(hipGetLastError(), "merkle launch") : 0;
@@ -252,7 +240,7 @@ uint64_t bcosgpu_merkle_bytes_size(uint64_t n, int width) {
 }
 
 int bcosgpu_merkle_tree_bytes_dev(int width, const uint8_t* d_tree, size_t n, uint8_t* d_out, void* stream) {
-    if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_width(width)) return rc;
     if (n == 0) return set_err(BCOSGPU_E_EMPTY, "Empty input");
     if (!d_tree || !d_out) return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_merkle_compact(d_tree, n, width, d_out, as_stream(stream));
@@ -261,45 +249,40 @@ int bcosgpu_merkle_tree_bytes_dev(int width, const uint8_t* d_tree, size_t n, ui
 
 int bcosgpu_merkle_root(int hasher, int width, int variant, const uint8_t* leaves32, size_t n,
                         uint8_t* root32, uint8_t* levels) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (!root32 || (n && !leaves32)) return set_err(BCOSGPU_E_ARG, "null pointer");
     const bool bytes_layout = variant == BCOSGPU_MERKLE_NEW_BYTES;
     if (bytes_layout) variant = BCOSGPU_MERKLE_NEW;
     if (variant == BCOSGPU_MERKLE_NEW) {
         if (n == 0) return set_err(BCOSGPU_E_EMPTY, "Empty input");
-        if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+        if (int rc = check_width(width)) return rc;
     } else if (variant != BCOSGPU_MERKLE_OLD) {
         return set_err(BCOSGPU_E_ARG, "bad variant");
     }
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
+    WsCall c;
+    if (c.rc) return c.rc;
     const uint64_t tree = variant == BCOSGPU_MERKLE_NEW ? bcosgpu_merkle_size(n, width) : merkle_size(n, 16) + 1;
-    HIP_OK(w->b[0].ensure(n * 32 + 32));
-    HIP_OK(w->b[1].ensure(tree * 32 + 32));
-    HIP_OK(w->b[2].ensure(32));
-    if (levels && bytes_layout) HIP_OK(w->b[3].ensure(tree * 32 + 32));
-    if (n) HIP_OK(hipMemcpyAsync(w->b[0].p, leaves32, n * 32, hipMemcpyHostToDevice, w->stream));
+    const bool compact = levels && bytes_layout;
+    HIP_OK(c.ensure({n * 32 + 32, tree * 32 + 32, 32, compact ? tree * 32 + 32 : 0}));
+    if (n) HIP_OK(c.h2d(0, leaves32, n * 32));
+    int rc;
     if (variant == BCOSGPU_MERKLE_NEW)
-        rc = launch_merkle(hasher, width, w->b[0].as<uint8_t>(), n, w->b[1].as<uint8_t>(), w->b[2].as<uint8_t>(), w->stream);
+        rc = launch_merkle(hasher, width, c.buf(0), n, c.buf(1), c.buf(2), c.stream());
     else
-        rc = launch_merkle_old(hasher, w->b[0].as<uint8_t>(), n, w->b[1].as<uint8_t>(), w->b[2].as<uint8_t>(), w->stream);
-    if (!rc && levels && bytes_layout)
-        rc = launch_merkle_compact(w->b[1].as<uint8_t>(), n, width, w->b[3].as<uint8_t>(), w->stream);
+        rc = launch_merkle_old(hasher, c.buf(0), n, c.buf(1), c.buf(2), c.stream());
+    if (!rc && compact) rc = launch_merkle_compact(c.buf(1), n, width, c.buf(3), c.stream());
     if (rc) return rc == BCOSGPU_E_ARG ? set_err(rc, "bad merkle arguments") : hip_err(hipGetLastError(), "merkle launch");
-    HIP_OK(hipMemcpyAsync(root32, w->b[2].p, 32, hipMemcpyDeviceToHost, w->stream));
-    if (levels && bytes_layout)
-        HIP_OK(hipMemcpyAsync(levels, w->b[3].p, bcosgpu_merkle_bytes_size(n, width), hipMemcpyDeviceToHost, w->stream));
+    HIP_OK(c.d2h(root32, 2, 32));
+    if (compact)
+        HIP_OK(c.d2h(levels, 3, bcosgpu_merkle_bytes_size(n, width)));
     else if (levels && variant == BCOSGPU_MERKLE_NEW)
-        HIP_OK(hipMemcpyAsync(levels, w->b[1].p, tree * 32, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+        HIP_OK(c.d2h(levels, 1, tree * 32));
+    return c.finish();
 }
 
 int bcosgpu_merkle_frontier_dev(int hasher, int width, const uint8_t* d_leaves32, size_t n, int levels,
                                 uint8_t* d_work, uint8_t* d_frontier, void* stream) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (n == 0) return set_err(BCOSGPU_E_EMPTY, "Empty input");
     if (width < 2 || width > 64 || levels < 1 || levels > 63) return set_err(BCOSGPU_E_ARG, "bad width/levels");
     if (!d_leaves32 || !d_work || !d_frontier) return set_err(BCOSGPU_E_ARG, "null pointer");
@@ -322,8 +305,8 @@ static int check_block_off(const uint64_t* block_off, size_t nblocks) {
 
 int bcosgpu_merkle_roots_batch_dev(int hasher, int width, const uint8_t* d_leaves32, const uint64_t* block_off,
                                    size_t nblocks, uint8_t* d_work, uint8_t* d_roots32, void* stream) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
-    if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_hasher(hasher)) return rc;
+    if (int rc = check_width(width)) return rc;
     if (nblocks == 0) return 0;
     if (int rc = check_block_off(block_off, nblocks)) return rc;
     if (!d_work || !d_roots32 || (block_off[nblocks] > block_off[0] && !d_leaves32))
@@ -335,26 +318,20 @@ int bcosgpu_merkle_roots_batch_dev(int hasher, int width, const uint8_t* d_leave
 
 int bcosgpu_merkle_roots_batch(int hasher, int width, const uint8_t* leaves32, const uint64_t* block_off,
                                size_t nblocks, uint8_t* roots32) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
-    if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_hasher(hasher)) return rc;
+    if (int rc = check_width(width)) return rc;
     if (nblocks == 0) return 0;
     if (int rc = check_block_off(block_off, nblocks)) return rc;
     const uint64_t total = block_off[nblocks] - block_off[0];
     if (!roots32 || (total && !leaves32)) return set_err(BCOSGPU_E_ARG, "null pointer");
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
-    HIP_OK(w->b[0].ensure(total * 32 + 32));
-    HIP_OK(w->b[1].ensure(merkle_roots_work_bytes(total, nblocks, width)));
-    HIP_OK(w->b[2].ensure(nblocks * 32));
-    if (total) HIP_OK(hipMemcpyAsync(w->b[0].p, leaves32, total * 32, hipMemcpyHostToDevice, w->stream));
-    rc = launch_merkle_roots_batch(hasher, width, w->b[0].as<uint8_t>(), block_off, nblocks, w->b[1].as<uint8_t>(),
-                                   w->b[2].as<uint8_t>(), w->stream);
-    if (rc) return hip_err(hipGetLastError(), "merkle roots launch");
-    HIP_OK(hipMemcpyAsync(roots32, w->b[2].p, nblocks * 32, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    WsCall c;
+    if (c.rc) return c.rc;
+    HIP_OK(c.ensure({total * 32 + 32, merkle_roots_work_bytes(total, nblocks, width), nblocks * 32}));
+    if (total) HIP_OK(c.h2d(0, leaves32, total * 32));
+    if (launch_merkle_roots_batch(hasher, width, c.buf(0), block_off, nblocks, c.buf(1), c.buf(2), c.stream()))
+        return hip_err(hipGetLastError(), "merkle roots launch");
+    HIP_OK(c.d2h(roots32, 2, nblocks * 32));
+    return c.finish();
 }
 
 // calculateReceiptRoot for many blocks (BlockImpl.h:156-183): the receipt preimages are packed
@@ -362,16 +339,15 @@ int bcosgpu_merkle_roots_batch(int hasher, int width, const uint8_t* leaves32, c
 // short-circuits (TarsHashable.h:47-51) patched in, then the many-tree root kernel.
 int bcosgpu_receipt_roots(int hasher, const bcosgpu_TransactionReceiptData* receipts, const uint64_t* block_off,
                           size_t nblocks, uint8_t* roots32, uint8_t* hashes32) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (nblocks == 0) return 0;
     if (int rc = check_block_off(block_off, nblocks)) return rc;
     if (block_off[0] != 0) return set_err(BCOSGPU_E_ARG, "block_off[0] must be 0");
     const uint64_t n = block_off[nblocks];
     if (!roots32 || (n && !receipts)) return set_err(BCOSGPU_E_ARG, "null pointer");
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
+    WsCall c;
+    if (c.rc) return c.rc;
+    Workspace* w = c.w;
     const uint64_t bytes = bcosgpu_receipt_preimage_size(receipts, n);
     bool patched = false;
     for (uint64_t i = 0; i < n && !patched; ++i) patched = receipts[i].data_hash_len != 0;
@@ -381,31 +357,26 @@ int bcosgpu_receipt_roots(int hasher, const bcosgpu_TransactionReceiptData* rece
     uint8_t* pre = reinterpret_cast<uint8_t*>(off + n + 1);
     if (bcosgpu_pack_receipt_preimages(receipts, n, pre, bytes, off))
         return set_err(BCOSGPU_E_ARG, "bad receipt view (null field with a length, or a dataHash over 32 bytes)");
-    HIP_OK(w->b[0].ensure(bytes + 8 * (n + 1) + 16));
-    HIP_OK(w->b[1].ensure(32 * n + 32));
-    HIP_OK(w->b[2].ensure(merkle_roots_work_bytes(n, nblocks, 2)));
-    HIP_OK(w->b[3].ensure(nblocks * 32));
-    uint8_t* d_hash = w->b[1].as<uint8_t>();
+    HIP_OK(c.ensure({bytes + 8 * (n + 1) + 16, 32 * n + 32, merkle_roots_work_bytes(n, nblocks, 2), nblocks * 32}));
+    uint8_t* d_hash = c.buf(1);
     if (n) {
-        HIP_OK(hipMemcpyAsync(w->b[0].p, off, bytes + 8 * (n + 1), hipMemcpyHostToDevice, w->stream));
-        const uint64_t* d_off = w->b[0].as<uint64_t>();
-        if (launch_hash_batch(hasher, reinterpret_cast<const uint8_t*>(d_off + n + 1), d_off, n, d_hash, w->stream))
+        HIP_OK(c.h2d(0, off, bytes + 8 * (n + 1)));
+        const uint64_t* d_off = c.buf<uint64_t>(0);
+        if (launch_hash_batch(hasher, reinterpret_cast<const uint8_t*>(d_off + n + 1), d_off, n, d_hash, c.stream()))
             return hip_err(hipGetLastError(), "receipt hash launch");
         if (patched) {  // the dataHash receipts: hashes round-trip through the host once
             uint8_t* h = w->h[1].as<uint8_t>();
-            HIP_OK(hipMemcpyAsync(h, d_hash, 32 * n, hipMemcpyDeviceToHost, w->stream));
-            HIP_OK(hipStreamSynchronize(w->stream));
+            HIP_OK(c.d2h(h, 1, 32 * n));
+            HIP_OK(hipStreamSynchronize(c.stream()));
             bcosgpu_apply_receipt_data_hashes(receipts, n, h);
-            HIP_OK(hipMemcpyAsync(d_hash, h, 32 * n, hipMemcpyHostToDevice, w->stream));
+            HIP_OK(c.h2d(1, h, 32 * n));
         }
     }
-    rc = launch_merkle_roots_batch(hasher, 2, d_hash, block_off, nblocks, w->b[2].as<uint8_t>(), w->b[3].as<uint8_t>(),
-                                   w->stream);
-    if (rc) return hip_err(hipGetLastError(), "merkle roots launch");
-    HIP_OK(hipMemcpyAsync(roots32, w->b[3].p, nblocks * 32, hipMemcpyDeviceToHost, w->stream));
-    if (hashes32 && n) HIP_OK(hipMemcpyAsync(hashes32, d_hash, 32 * n, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    if (launch_merkle_roots_batch(hasher, 2, d_hash, block_off, nblocks, c.buf(2), c.buf(3), c.stream()))
+        return hip_err(hipGetLastError(), "merkle roots launch");
+    HIP_OK(c.d2h(roots32, 3, nblocks * 32));
+    if (hashes32 && n) HIP_OK(c.d2h(hashes32, 1, 32 * n));
+    return c.finish();
 }
 
 // ------------------------------------------------------------------ Merkle proofs
@@ -416,7 +387,7 @@ uint64_t bcosgpu_merkle_proof_stride(uint64_t n, int width) {
 
 int bcosgpu_merkle_proofs_dev(int width, const uint8_t* d_leaves32, size_t n, const uint8_t* d_tree,
                               const uint64_t* d_index, size_t m, uint8_t* d_proofs, uint32_t* d_proof_len, void* stream) {
-    if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_width(width)) return rc;
     if (n == 0) return set_err(BCOSGPU_E_EMPTY, "Empty input");
     if (m && (!d_leaves32 || !d_tree || !d_index || !d_proofs || !d_proof_len)) return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_merkle_proofs(width, d_leaves32, n, d_tree, d_index, m, d_proofs, d_proof_len, as_stream(stream));
@@ -425,40 +396,31 @@ int bcosgpu_merkle_proofs_dev(int width, const uint8_t* d_leaves32, size_t n, co
 
 int bcosgpu_merkle_proofs(int hasher, int width, const uint8_t* leaves32, size_t n, const uint64_t* index, size_t m,
                           uint8_t* proofs, uint32_t* proof_len) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
-    if (width < 2 || width > 64) return set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_hasher(hasher)) return rc;
+    if (int rc = check_width(width)) return rc;
     if (n == 0) return set_err(BCOSGPU_E_EMPTY, "Empty input");
     if (m == 0) return 0;
     if (!leaves32 || !index || !proofs || !proof_len) return set_err(BCOSGPU_E_ARG, "null pointer");
     for (size_t q = 0; q < m; ++q)
         if (index[q] >= n) return set_err(BCOSGPU_E_ARG, "Out of range!");  // Merkle.h:124-127
     const uint64_t stride = merkle_proof_stride(n, width), tree = bcosgpu_merkle_size(n, width);
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
-    HIP_OK(w->b[0].ensure(n * 32));
-    HIP_OK(w->b[1].ensure(tree * 32 + 32));
-    HIP_OK(w->b[2].ensure(m * 8));
-    HIP_OK(w->b[3].ensure(m * stride * 32));
-    HIP_OK(w->b[4].ensure(m * 4));
-    HIP_OK(hipMemcpyAsync(w->b[0].p, leaves32, n * 32, hipMemcpyHostToDevice, w->stream));
-    HIP_OK(hipMemcpyAsync(w->b[2].p, index, m * 8, hipMemcpyHostToDevice, w->stream));
-    rc = launch_merkle(hasher, width, w->b[0].as<uint8_t>(), n, w->b[1].as<uint8_t>(), nullptr, w->stream);
-    if (!rc)
-        rc = launch_merkle_proofs(width, w->b[0].as<uint8_t>(), n, w->b[1].as<uint8_t>(), w->b[2].as<uint64_t>(), m,
-                                  w->b[3].as<uint8_t>(), w->b[4].as<uint32_t>(), w->stream);
-    if (rc) return hip_err(hipGetLastError(), "merkle proofs launch");
-    HIP_OK(hipMemcpyAsync(proofs, w->b[3].p, m * stride * 32, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipMemcpyAsync(proof_len, w->b[4].p, m * 4, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    WsCall c;
+    if (c.rc) return c.rc;
+    HIP_OK(c.ensure({n * 32, tree * 32 + 32, m * 8, m * stride * 32, m * 4}));
+    HIP_OK(c.h2d(0, leaves32, n * 32));
+    HIP_OK(c.h2d(2, index, m * 8));
+    if (launch_merkle(hasher, width, c.buf(0), n, c.buf(1), nullptr, c.stream()) ||
+        launch_merkle_proofs(width, c.buf(0), n, c.buf(1), c.buf<uint64_t>(2), m, c.buf(3), c.buf<uint32_t>(4), c.stream()))
+        return hip_err(hipGetLastError(), "merkle proofs launch");
+    HIP_OK(c.d2h(proofs, 3, m * stride * 32));
+    HIP_OK(c.d2h(proof_len, 4, m * 4));
+    return c.finish();
 }
 
 int bcosgpu_merkle_verify_proofs_dev(int hasher, const uint8_t* d_proofs, uint64_t stride, const uint32_t* d_proof_len,
                                      const uint8_t* d_hashes32, const uint8_t* d_roots32, int per_proof_root, size_t m,
                                      uint8_t* d_ok, void* stream) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (stride == 0 || stride > 0xFFFFFFFFull) return set_err(BCOSGPU_E_ARG, "bad proof stride");
     if (m && (!d_proofs || !d_proof_len || !d_hashes32 || !d_roots32 || !d_ok)) return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_merkle_verify(hasher, d_proofs, stride, d_proof_len, d_hashes32, d_roots32, per_proof_root ? 1 : 0, m,
@@ -468,30 +430,23 @@ int bcosgpu_merkle_verify_proofs_dev(int hasher, const uint8_t* d_proofs, uint64
 
 int bcosgpu_merkle_verify_proofs(int hasher, const uint8_t* proofs, uint64_t stride, const uint32_t* proof_len,
                                  const uint8_t* hashes32, const uint8_t* roots32, int per_proof_root, size_t m, uint8_t* ok) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return set_err(BCOSGPU_E_ARG, "bad hasher");
+    if (int rc = check_hasher(hasher)) return rc;
     if (stride == 0 || stride > 0xFFFFFFFFull) return set_err(BCOSGPU_E_ARG, "bad proof stride");
     if (m == 0) return 0;
     if (!proofs || !proof_len || !hashes32 || !roots32 || !ok) return set_err(BCOSGPU_E_ARG, "null pointer");
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
+    WsCall c;
+    if (c.rc) return c.rc;
     const size_t nroots = per_proof_root ? m : 1;
-    HIP_OK(w->b[0].ensure(m * stride * 32));
-    HIP_OK(w->b[1].ensure(m * 4));
-    HIP_OK(w->b[2].ensure(m * 32));
-    HIP_OK(w->b[3].ensure(nroots * 32));
-    HIP_OK(w->b[4].ensure(m));
-    HIP_OK(hipMemcpyAsync(w->b[0].p, proofs, m * stride * 32, hipMemcpyHostToDevice, w->stream));
-    HIP_OK(hipMemcpyAsync(w->b[1].p, proof_len, m * 4, hipMemcpyHostToDevice, w->stream));
-    HIP_OK(hipMemcpyAsync(w->b[2].p, hashes32, m * 32, hipMemcpyHostToDevice, w->stream));
-    HIP_OK(hipMemcpyAsync(w->b[3].p, roots32, nroots * 32, hipMemcpyHostToDevice, w->stream));
-    rc = launch_merkle_verify(hasher, w->b[0].as<uint8_t>(), stride, w->b[1].as<uint32_t>(), w->b[2].as<uint8_t>(),
-                              w->b[3].as<uint8_t>(), per_proof_root ? 1 : 0, m, w->b[4].as<uint8_t>(), w->stream);
-    if (rc) return hip_err(hipGetLastError(), "merkle verify launch");
-    HIP_OK(hipMemcpyAsync(ok, w->b[4].p, m, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    HIP_OK(c.ensure({m * stride * 32, m * 4, m * 32, nroots * 32, m}));
+    HIP_OK(c.h2d(0, proofs, m * stride * 32));
+    HIP_OK(c.h2d(1, proof_len, m * 4));
+    HIP_OK(c.h2d(2, hashes32, m * 32));
+    HIP_OK(c.h2d(3, roots32, nroots * 32));
+    if (launch_merkle_verify(hasher, c.buf(0), stride, c.buf<uint32_t>(1), c.buf(2), c.buf(3), per_proof_root ? 1 : 0, m,
+                             c.buf(4), c.stream()))
+        return hip_err(hipGetLastError(), "merkle verify launch");
+    HIP_OK(c.d2h(ok, 4, m));
+    return c.finish();
 }
 
 // ------------------------------------------------------------------ signatures
@@ -509,15 +464,7 @@ int bcosgpu_secp256k1_recover_batch(const uint8_t* hash32, const uint8_t* sig65,
     if (!hash32 || !sig65 || !ok) return set_err(BCOSGPU_E_ARG, "null pointer");
     int dev = 0;
     if (int rc = calling_device(&dev)) return rc;
-    SigJob job;
-    job.kind = kSigJobRecoverK1;
-    job.n = n;
-    job.hash32 = hash32;
-    job.sig = sig65;
-    job.sig_stride = 65;
-    job.out_pub64 = pub64;
-    job.out_addr20 = addr20;
-    job.out_ok = ok;
+    SigJob job = sig_job(kSigJobRecoverK1, n, hash32, sig65, 65, nullptr, pub64, addr20, ok);
     return run_job(dev, job);
 }
 
@@ -534,14 +481,7 @@ int bcosgpu_sm2_verify_batch(const uint8_t* hash32, const uint8_t* sig128, size_
     if (!hash32 || !sig128 || !ok) return set_err(BCOSGPU_E_ARG, "null pointer");
     int dev = 0;
     if (int rc = calling_device(&dev)) return rc;
-    SigJob job;
-    job.kind = kSigJobVerifySM2;
-    job.n = n;
-    job.hash32 = hash32;
-    job.sig = sig128;
-    job.sig_stride = 128;
-    job.out_addr20 = addr20;
-    job.out_ok = ok;
+    SigJob job = sig_job(kSigJobVerifySM2, n, hash32, sig128, 128, nullptr, nullptr, addr20, ok);
     return run_job(dev, job);
 }
 
@@ -562,8 +502,8 @@ int bcosgpu_sm2_sign_batch_dev(const uint8_t* d_sk32, const uint8_t* d_hash32, s
 // ------------------------------------------------------------------ verify with a known key, ecRecover
 int bcosgpu_verify_batch_dev(int suite, const uint8_t* d_pub64, const uint8_t* d_hash32, const uint8_t* d_sig,
                              size_t sig_stride, size_t n, uint8_t* d_ok, void* stream) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
-    if (sig_stride < 64 || sig_stride > 0xFFFFFFFFull) return set_err(BCOSGPU_E_ARG, "signature stride must be >= 64");
+    if (int rc = check_suite(suite)) return rc;
+    if (int rc = check_stride(sig_stride)) return rc;
     if (n && (!d_pub64 || !d_hash32 || !d_sig || !d_ok)) return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_sig_verify(suite, d_pub64, d_hash32, d_sig, static_cast<uint32_t>(sig_stride), n, d_ok,
                                as_stream(stream));
@@ -572,38 +512,26 @@ int bcosgpu_verify_batch_dev(int suite, const uint8_t* d_pub64, const uint8_t* d
 
 int bcosgpu_verify_batch(int suite, const uint8_t* pub64, const uint8_t* hash32, const uint8_t* sig,
                          size_t sig_stride, size_t n, uint8_t* ok) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
-    if (sig_stride < 64 || sig_stride > 0xFFFFFFFFull) return set_err(BCOSGPU_E_ARG, "signature stride must be >= 64");
+    if (int rc = check_suite(suite)) return rc;
+    if (int rc = check_stride(sig_stride)) return rc;
     if (n == 0) return 0;
     if (!pub64 || !hash32 || !sig || !ok) return set_err(BCOSGPU_E_ARG, "null pointer");
     int dev = 0;
     if (int rc = calling_device(&dev)) return rc;
-    SigJob job;
-    job.kind = suite == BCOSGPU_SUITE_SM2 ? kSigJobVerifySM2 : kSigJobVerifyK1;
-    job.n = n;
-    job.hash32 = hash32;
-    job.sig = sig;
-    job.sig_stride = sig_stride;
-    job.pub64 = pub64;
-    job.out_ok = ok;
+    SigJob job = sig_job(suite == BCOSGPU_SUITE_SM2 ? kSigJobVerifySM2 : kSigJobVerifyK1, n, hash32, sig, sig_stride, pub64,
+                         nullptr, nullptr, ok);
     return run_job(dev, job);
 }
 
 // ------------------------------------------------------------------ registered keys (ecc_keyed.hip)
 int bcosgpu_register_keys(int device, int suite, const uint8_t* pub64, size_t n, int32_t* slots) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     if (n && (!pub64 || !slots)) return set_err(BCOSGPU_E_ARG, "null pointer");
     if (int rc = ready_device(device)) return rc;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) {
-        (void)hipGetLastError();
-        prev = -1;
-    }
-    if (prev != device && hipSetDevice(device) != hipSuccess) return set_err(BCOSGPU_E_HIP, "hipSetDevice failed");
+    DeviceScope on(device);
+    if (on.err != hipSuccess) return set_err(BCOSGPU_E_HIP, "hipSetDevice failed");
     bool all = false;
-    const int rc = keyed_slots(suite, pub64, 64, n, slots, true, &all, nullptr);
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (rc) return set_err(rc, "key table build failed");
+    if (int rc = keyed_slots(suite, pub64, 64, n, slots, true, &all, nullptr)) return set_err(rc, "key table build failed");
     int cached = 0;
     for (size_t i = 0; i < n; ++i) cached += slots[i] >= 0;
     return cached;
@@ -611,8 +539,8 @@ int bcosgpu_register_keys(int device, int suite, const uint8_t* pub64, size_t n,
 
 int bcosgpu_verify_keyed_batch_dev(int suite, const int32_t* d_slots, const uint8_t* d_hash32, const uint8_t* d_sig,
                                    size_t sig_stride, size_t n, uint8_t* d_ok, void* stream) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
-    if (sig_stride < 64 || sig_stride > 0xFFFFFFFFull) return set_err(BCOSGPU_E_ARG, "signature stride must be >= 64");
+    if (int rc = check_suite(suite)) return rc;
+    if (int rc = check_stride(sig_stride)) return rc;
     if (n && (!d_slots || !d_hash32 || !d_sig || !d_ok)) return set_err(BCOSGPU_E_ARG, "null pointer");
     const int rc = launch_sig_verify_keyed(suite, d_slots, d_hash32, d_sig, static_cast<uint32_t>(sig_stride), n, d_ok,
                                            nullptr, as_stream(stream));
@@ -620,14 +548,14 @@ int bcosgpu_verify_keyed_batch_dev(int suite, const int32_t* d_slots, const uint
 }
 
 int bcosgpu_key_cache_info(int device, int suite, int64_t* out5) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     if (!out5) return set_err(BCOSGPU_E_ARG, "null pointer");
     const int rc = keyed_cache_info(device, suite, out5);
     return rc ? set_err(rc, "bad device") : 0;
 }
 
 int bcosgpu_clear_keys(int device, int suite) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     const int rc = keyed_clear(device, suite);
     return rc ? set_err(rc, "clearing the key cache failed") : 0;
 }
@@ -641,20 +569,14 @@ int bcosgpu_ecrecover_batch_dev(const uint8_t* d_in128, size_t n, uint8_t* d_out
 int bcosgpu_ecrecover_batch(const uint8_t* in128, size_t n, uint8_t* out32, uint8_t* ok) {
     if (n == 0) return 0;
     if (!in128 || !out32 || !ok) return set_err(BCOSGPU_E_ARG, "null pointer");
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
-    HIP_OK(w->b[0].ensure(n * 128));
-    HIP_OK(w->b[1].ensure(n * 32));
-    HIP_OK(w->b[2].ensure(n));
-    HIP_OK(hipMemcpyAsync(w->b[0].p, in128, n * 128, hipMemcpyHostToDevice, w->stream));
-    rc = launch_ecrecover(w->b[0].as<uint8_t>(), n, w->b[1].as<uint8_t>(), w->b[2].as<uint8_t>(), w->stream);
-    if (rc) return set_err(rc, "ecrecover launch failed");
-    HIP_OK(hipMemcpyAsync(out32, w->b[1].p, n * 32, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipMemcpyAsync(ok, w->b[2].p, n, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    WsCall c;
+    if (c.rc) return c.rc;
+    HIP_OK(c.ensure({n * 128, n * 32, n}));
+    HIP_OK(c.h2d(0, in128, n * 128));
+    if (int rc = launch_ecrecover(c.buf(0), n, c.buf(1), c.buf(2), c.stream())) return set_err(rc, "ecrecover launch failed");
+    HIP_OK(c.d2h(out32, 1, n * 32));
+    HIP_OK(c.d2h(ok, 2, n));
+    return c.finish();
 }
 
 // ------------------------------------------------------------------ whole-tx admission
@@ -662,7 +584,7 @@ int bcosgpu_tx_verify_batch_dev(int suite, const uint8_t* d_pre, const uint64_t*
                                 const uint8_t* d_sig, const uint64_t* d_sig_off, size_t n,
                                 uint8_t* d_txhash32, uint8_t* d_sender20, uint8_t* d_status,
                                 void* stream) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     if (n && (!d_pre || !d_pre_off || !d_sig || !d_sig_off || !d_txhash32 || !d_sender20 || !d_status))
         return set_err(BCOSGPU_E_ARG, "null pointer");
     int rc = launch_tx_verify(suite, d_pre, d_pre_off, d_sig, d_sig_off, n, d_txhash32, d_sender20, d_status,
@@ -676,7 +598,7 @@ int bcosgpu_tx_verify_batch_dev(int suite, const uint8_t* d_pre, const uint64_t*
 int bcosgpu_tx_verify_batch(int suite, const uint8_t* pre, const uint64_t* pre_off,
                             const uint8_t* sig, const uint64_t* sig_off, size_t n,
                             uint8_t* txhash32, uint8_t* sender20, uint8_t* status) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     if (n == 0) return 0;
     if (!pre || !pre_off || !sig || !sig_off || !txhash32 || !sender20 || !status)
         return set_err(BCOSGPU_E_ARG, "null pointer");
@@ -684,18 +606,8 @@ int bcosgpu_tx_verify_batch(int suite, const uint8_t* pre, const uint64_t* pre_o
     if (int rc = calling_device(&dev)) return rc;
     TxPipe* p = tx_pipe_acquire(dev);
     if (!p) return hip_err(hipGetLastError(), "tx pipeline setup");
-    HostTxRange t;
-    t.suite = suite;
-    t.pre = pre;
-    t.pre_off = pre_off;
-    t.sig = sig;
-    t.sig_off = sig_off;
-    t.lo = 0;
-    t.hi = n;
-    t.txhash32 = txhash32;
-    t.sender20 = sender20;
-    t.status = status;
     std::string msg;
+    const HostTxRange t = host_range(suite, pre, pre_off, sig, sig_off, 0, n, txhash32, sender20, status);
     const int rc = tx_pipeline(*p, t, nullptr, msg);
     tx_pipe_release(p);
     return rc ? set_err(rc, msg) : 0;
@@ -720,7 +632,7 @@ int bcosgpu_tars_tx_verify_batch_dev(int suite, const uint8_t* d_enc, const uint
                                      int check_sig, int check_hash, uint8_t* d_pre, uint64_t* d_pre_off, uint8_t* d_sig,
                                      uint64_t* d_sig_off, void* d_work, uint64_t work_bytes, uint8_t* d_txhash32,
                                      uint8_t* d_sender20, uint8_t* d_status, void* stream) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     if (n == 0) return 0;
     if (!d_enc || !d_enc_off || !d_pre || !d_pre_off || !d_sig || !d_sig_off || !d_work || !d_txhash32 ||
         !d_sender20 || !d_status)
@@ -744,40 +656,31 @@ int bcosgpu_tars_tx_verify_batch_dev(int suite, const uint8_t* d_enc, const uint
 
 int bcosgpu_tars_tx_verify_batch(int suite, const uint8_t* enc, const uint64_t* enc_off, size_t n, int check_sig,
                                  int check_hash, uint8_t* txhash32, uint8_t* sender20, uint8_t* status) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return set_err(BCOSGPU_E_ARG, "bad suite");
+    if (int rc = check_suite(suite)) return rc;
     if (n == 0) return 0;
     if (!enc || !enc_off || !txhash32 || !sender20 || !status) return set_err(BCOSGPU_E_ARG, "null pointer");
     for (size_t i = 0; i < n; ++i)
         if (enc_off[i + 1] < enc_off[i]) return set_err(BCOSGPU_E_ARG, "offsets must be non-decreasing");
     const uint64_t base = enc_off[0], bytes = enc_off[n] - base;
-    Workspace* w;
-    int rc = get_ws(&w);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> g(w->mu);
-    const uint64_t work = tars_decode_work_bytes(n);
-    HIP_OK(w->b[0].ensure(bytes + 8));
-    HIP_OK(w->b[1].ensure((n + 1) * 8));
-    HIP_OK(w->b[2].ensure(bytes + 12 * n + 8));  // preimages
-    HIP_OK(w->b[3].ensure(2 * (n + 1) * 8));     // preimage + signature offsets
-    HIP_OK(w->b[4].ensure(bytes + 8));           // signatures
-    HIP_OK(w->b[5].ensure(n * 53));              // txhash, sender, status
-    HIP_OK(w->b[6].ensure(work));
-    std::vector<uint64_t> off(n + 1);
+    std::vector<uint64_t> off(n + 1);  // (declared before the call: the drain runs while it is alive)
     for (size_t i = 0; i <= n; ++i) off[i] = enc_off[i] - base;
-    HIP_OK(hipMemcpyAsync(w->b[0].p, enc + base, bytes, hipMemcpyHostToDevice, w->stream));
-    HIP_OK(hipMemcpyAsync(w->b[1].p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, w->stream));
-    uint64_t* pre_off = w->b[3].as<uint64_t>();
-    uint8_t* out = w->b[5].as<uint8_t>();
-    rc = bcosgpu_tars_tx_verify_batch_dev(suite, w->b[0].as<uint8_t>(), w->b[1].as<uint64_t>(), n, check_sig,
-                                          check_hash,
-                                          w->b[2].as<uint8_t>(), pre_off, w->b[4].as<uint8_t>(), pre_off + (n + 1),
-                                          w->b[6].p, work, out, out + 32 * n, out + 52 * n, w->stream);
-    if (rc) return rc;
-    HIP_OK(hipMemcpyAsync(txhash32, out, n * 32, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipMemcpyAsync(sender20, out + 32 * n, n * 20, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipMemcpyAsync(status, out + 52 * n, n, hipMemcpyDeviceToHost, w->stream));
-    HIP_OK(hipStreamSynchronize(w->stream));
-    return 0;
+    WsCall c;
+    if (c.rc) return c.rc;
+    const uint64_t work = tars_decode_work_bytes(n);
+    // encoded txs, their offsets | preimages, preimage + signature offsets, signatures | txhash, sender, status | work
+    HIP_OK(c.ensure({bytes + 8, (n + 1) * 8, bytes + 12 * n + 8, 2 * (n + 1) * 8, bytes + 8, n * 53, work}));
+    HIP_OK(c.h2d(0, enc + base, bytes));
+    HIP_OK(c.h2d(1, off.data(), (n + 1) * 8));
+    uint64_t* pre_off = c.buf<uint64_t>(3);
+    uint8_t* out = c.buf(5);
+    if (int rc = bcosgpu_tars_tx_verify_batch_dev(suite, c.buf(0), c.buf<uint64_t>(1), n, check_sig, check_hash, c.buf(2),
+                                                  pre_off, c.buf(4), pre_off + (n + 1), c.buf<void>(6), work, out,
+                                                  out + 32 * n, out + 52 * n, c.stream()))
+        return rc;
+    HIP_OK(hipMemcpyAsync(txhash32, out, n * 32, hipMemcpyDeviceToHost, c.stream()));
+    HIP_OK(hipMemcpyAsync(sender20, out + 32 * n, n * 20, hipMemcpyDeviceToHost, c.stream()));
+    HIP_OK(hipMemcpyAsync(status, out + 52 * n, n, hipMemcpyDeviceToHost, c.stream()));
+    return c.finish();
 }
 
 // ------------------------------------------------------------------ single calls (coalesced)
@@ -789,14 +692,7 @@ int bcosgpu_secp256k1_recover(int device, const uint8_t* hash32, const uint8_t* 
         return 0;
     }
     uint8_t ok = 0;
-    SigJob job;
-    job.kind = kSigJobRecoverK1;
-    job.n = 1;
-    job.hash32 = hash32;
-    job.sig = sig;
-    job.sig_stride = 65;
-    job.out_pub64 = pub64;
-    job.out_ok = &ok;
+    SigJob job = sig_job(kSigJobRecoverK1, 1, hash32, sig, 65, nullptr, pub64, nullptr, &ok);
     if (int rc = run_job(device, job)) return rc;
     return ok ? 1 : 0;
 }
@@ -807,14 +703,7 @@ int bcosgpu_secp256k1_verify(int device, const uint8_t* pub64, const uint8_t* ha
     if (int rc = ready_device(device)) return rc;
     if (sig_len < 64) return 0;
     uint8_t ok = 0;
-    SigJob job;
-    job.kind = kSigJobVerifyK1;
-    job.n = 1;
-    job.hash32 = hash32;
-    job.sig = sig;
-    job.sig_stride = 64;
-    job.pub64 = pub64;
-    job.out_ok = &ok;
+    SigJob job = sig_job(kSigJobVerifyK1, 1, hash32, sig, 64, pub64, nullptr, nullptr, &ok);
     if (int rc = run_job(device, job)) return rc;
     return ok ? 1 : 0;
 }
@@ -823,14 +712,7 @@ int bcosgpu_sm2_verify(int device, const uint8_t* pub64, const uint8_t* hash32, 
     if (!pub64 || !hash32 || !sig64) return set_err(BCOSGPU_E_ARG, "null pointer");
     if (int rc = ready_device(device)) return rc;
     uint8_t ok = 0;
-    SigJob job;
-    job.kind = kSigJobVerifySM2;
-    job.n = 1;
-    job.hash32 = hash32;
-    job.sig = sig64;
-    job.sig_stride = 64;
-    job.pub64 = pub64;
-    job.out_ok = &ok;
+    SigJob job = sig_job(kSigJobVerifySM2, 1, hash32, sig64, 64, pub64, nullptr, nullptr, &ok);
     if (int rc = run_job(device, job)) return rc;
     return ok ? 1 : 0;
 }

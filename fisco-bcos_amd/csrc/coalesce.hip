@@ -90,14 +90,9 @@ struct Slot {
     bool busy = false;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;  // wait modes 1 and 2
-    uint8_t* h_in = nullptr;  // pinned, device-mapped staging
-    uint8_t* h_out = nullptr;
-    uint8_t* hd_in = nullptr;  // their device addresses (zero-copy small batches)
-    uint8_t* hd_out = nullptr;
-    size_t h_in_cap = 0, h_out_cap = 0;
-    uint8_t* d_in = nullptr;
-    uint8_t* d_out = nullptr;
-    size_t d_in_cap = 0, d_out_cap = 0;
+    PinnedBuf h_in{true}, h_out{true};  // device-mapped staging (hd: zero-copy small batches)
+    DevBuf d_in, d_out;                 // batches past the zero-copy size (64 KiB floor, as the staging)
+    Slot() { d_in.min = d_out.min = 65536; }
 };
 
 // Where a coalesced call's time goes (bcosgpu_coalesce_stats): per device, summed over calls / batches,
@@ -149,35 +144,10 @@ DeviceQueue* queue_of(int device) {
     return g_queues[device];
 }
 
-size_t grow(size_t want) { return want < 65536 ? 65536 : want + want / 4; }
-
-hipError_t ensure_pinned(uint8_t*& p, uint8_t*& dp, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = dp = nullptr;
-    cap = 0;
-    const size_t want = grow(bytes);
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&dp), p, 0);
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
 // Batches up to this many items are read and written by the kernel in place, in the mapped staging
 // (zero-copy: no copy dispatches, which cost a latency-bound single call ~2 x 20-60 us of queue time);
 // larger ones are copied by the DMA engines.
 constexpr size_t kZeroCopyMax = 2048;
-
-hipError_t ensure_dev(uint8_t*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = grow(bytes);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want);
-    if (e == hipSuccess) cap = want;
-    return e;
-}
 
 // Bytes per item of the staged input and output of each job kind.
 //   recover secp256k1: in  hash[32] .. | sig[65] ..          out pub[64] .. | addr[20] .. | ok ..
@@ -197,7 +167,7 @@ int fail(std::vector<SigJob*>& batch, int rc, const std::string& msg) {
 #define BATCH_HIP(call)                                                                        \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) return fail(batch, BCOSGPU_E_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return fail(batch, BCOSGPU_E_HIP, hip_msg(e_, #call));           \
     } while (0)
 
 // One coalesced launch for `batch` (all of one kind) on `slot` of `device`.
@@ -211,15 +181,8 @@ int run_batch(int device, int kind, Slot& slot, std::vector<SigJob*>& batch, std
         want_addr = want_addr || j->out_addr20;
         want_pub = want_pub || j->out_pub64;
     }
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != device) BATCH_HIP(hipSetDevice(device));
-    struct Restore {
-        int prev, dev;
-        ~Restore() {
-            if (prev != dev) (void)hipSetDevice(prev);
-        }
-    } restore{prev, device};
+    DeviceScope select_device(device);
+    BATCH_HIP(select_device.err);
     if (!slot.stream) {
         // Streams of one priority share a few hardware queues (GPU_MAX_HW_QUEUES), and kernels on one
         // queue run in order, so slot k takes priority level k mod levels: each level brings its own
@@ -237,19 +200,19 @@ int run_batch(int device, int kind, Slot& slot, std::vector<SigJob*>& batch, std
     const bool verify = kind == kSigJobVerifyK1 || kind == kSigJobVerifySM2;
     const size_t slots_at = kInPer[kind] * n;
     const size_t in_bytes = slots_at + (verify ? 4 * n : 0), out_bytes = kOutPer[kind] * n;
-    BATCH_HIP(ensure_pinned(slot.h_in, slot.hd_in, slot.h_in_cap, in_bytes));
-    BATCH_HIP(ensure_pinned(slot.h_out, slot.hd_out, slot.h_out_cap, out_bytes));
+    BATCH_HIP(slot.h_in.ensure(in_bytes));
+    BATCH_HIP(slot.h_out.ensure(out_bytes));
     static const size_t zero_copy_max = [] {
         const char* e = getenv("BCOSGPU_COALESCE_ZEROCOPY");  // items; tuning
         return e ? static_cast<size_t>(atol(e)) : kZeroCopyMax;
     }();
     const bool zero_copy = n <= zero_copy_max;
     if (!zero_copy) {
-        BATCH_HIP(ensure_dev(slot.d_in, slot.d_in_cap, in_bytes + 16));
-        BATCH_HIP(ensure_dev(slot.d_out, slot.d_out_cap, out_bytes + 16));
+        BATCH_HIP(slot.d_in.ensure(in_bytes + 16));
+        BATCH_HIP(slot.d_out.ensure(out_bytes + 16));
     }
     // assemble the SoA input
-    uint8_t* in = slot.h_in;
+    uint8_t* in = slot.h_in.as<uint8_t>();
     size_t at = 0;
     for (SigJob* j : batch) {
         const size_t m = j->n;
@@ -291,9 +254,11 @@ int run_batch(int device, int kind, Slot& slot, std::vector<SigJob*>& batch, std
                                     reinterpret_cast<int32_t*>(in + slots_at), false, &keyed, slot.stream, &gen, named);
         if (krc) keyed = false;  // a failed table build leaves the generic path
     }
-    if (!zero_copy) BATCH_HIP(hipMemcpyAsync(slot.d_in, slot.h_in, in_bytes, hipMemcpyHostToDevice, slot.stream));
-    const uint8_t* di = zero_copy ? slot.hd_in : slot.d_in;
-    uint8_t* dout = zero_copy ? slot.hd_out : slot.d_out;
+    // the slot goes back to the queue with its stream idle, whatever way the batch ends
+    StreamDrain drain(slot.stream);
+    if (!zero_copy) BATCH_HIP(hipMemcpyAsync(slot.d_in.p, in, in_bytes, hipMemcpyHostToDevice, slot.stream));
+    const uint8_t* di = static_cast<const uint8_t*>(zero_copy ? slot.h_in.hd : slot.d_in.p);
+    uint8_t* dout = static_cast<uint8_t*>(zero_copy ? slot.h_out.hd : slot.d_out.p);
     t_launch = now_ns();
     for (int attempt = 0; attempt < 2; ++attempt) {
         int rc;
@@ -315,7 +280,7 @@ int run_batch(int device, int kind, Slot& slot, std::vector<SigJob*>& batch, std
             return fail(batch, rc, std::string("signature batch launch failed: ") + hipGetErrorString(e));
         }
         if (!zero_copy)
-            BATCH_HIP(hipMemcpyAsync(slot.h_out, slot.d_out, out_bytes, hipMemcpyDeviceToHost, slot.stream));
+            BATCH_HIP(hipMemcpyAsync(slot.h_out.p, slot.d_out.p, out_bytes, hipMemcpyDeviceToHost, slot.stream));
         if (wait_mode() == 0) {
             BATCH_HIP(hipStreamSynchronize(slot.stream));
         } else {
@@ -353,9 +318,10 @@ int run_batch(int device, int kind, Slot& slot, std::vector<SigJob*>& batch, std
         if (!keyed || keyed_generation(vsuite) == gen) break;
         keyed = false;
     }
+    drain.dismiss();
     t_synced = now_ns();
     // scatter
-    const uint8_t* out = slot.h_out;
+    const uint8_t* out = slot.h_out.as<uint8_t>();
     at = 0;
     for (SigJob* j : batch) {
         const size_t m = j->n;

@@ -813,12 +813,8 @@ int keyed_clear(int device, int suite) {
     if (device < 0 || device >= 64) return BCOSGPU_E_ARG;
     KeyCache& c = *cache_of(device, suite == BCOSGPU_SUITE_SM2 ? 1 : 0);
     std::lock_guard<std::mutex> g(c.mu);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != device && hipSetDevice(device) != hipSuccess) return BCOSGPU_E_HIP;
-    const hipError_t e = hipDeviceSynchronize();
-    if (prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return BCOSGPU_E_HIP;
+    DeviceScope on(device);
+    if (on.err != hipSuccess || hipDeviceSynchronize() != hipSuccess) return BCOSGPU_E_HIP;
     c.slot_of.clear();
     c.pending.clear();  // the device drained: a build in flight has completed, and is dropped unpublished
     c.building = false;

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/bcos_gpu.h"
+#include "host_rt.h"
 
 namespace bcosgpu {
 
@@ -97,6 +98,11 @@ struct SigJob {
     std::atomic<uint32_t> wake{0};       // the owner's futex word: bit 0 woken to lead, bit 1 done (coalesce.hip)
     SigJob* next = nullptr;              // the device queue's lock-free arrival stack
 };
+// (an aggregate: the engine's fields keep their defaults)
+inline SigJob sig_job(int kind, size_t n, const uint8_t* hash32, const uint8_t* sig, size_t sig_stride,
+                      const uint8_t* pub64, uint8_t* out_pub64, uint8_t* out_addr20, uint8_t* out_ok) {
+    return SigJob{kind, n, hash32, sig, sig_stride, pub64, out_pub64, out_addr20, out_ok};
+}
 int coalesced_run(int device, SigJob& job);
 int coalesce_stats(int device, uint64_t* out, int n, int reset);
 
@@ -105,27 +111,28 @@ int coalesce_stats(int device, uint64_t* out, int n, int reset);
 int api_set_err(int code, const std::string& msg);
 int api_ready_device(int device);
 int api_run_job(int device, SigJob& job);
+// the argument checks the entry points repeat (0, or E_ARG with the message set)
+inline int check_hasher(int hasher) {
+    return hasher == BCOSGPU_KECCAK256 || hasher == BCOSGPU_SM3 ? 0 : api_set_err(BCOSGPU_E_ARG, "bad hasher");
+}
+inline int check_suite(int suite) {
+    return suite == BCOSGPU_SUITE_SECP256K1 || suite == BCOSGPU_SUITE_SM2 ? 0 : api_set_err(BCOSGPU_E_ARG, "bad suite");
+}
+inline int check_width(int width) {
+    return width >= 2 && width <= 64 ? 0 : api_set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+}
+inline int check_stride(size_t sig_stride) {
+    return sig_stride >= 64 && sig_stride <= 0xFFFFFFFFull ? 0
+                                                           : api_set_err(BCOSGPU_E_ARG, "signature stride must be >= 64");
+}
 
 // txpipe.hip: the host-pointer tx-verify batches as a chunked copy / compute pipeline (see the file header)
-struct PipeBuf {  // grow-only device buffer
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes);
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-struct PipeHostBuf {  // grow-only pinned host buffer, mapped into the device's address space (hd)
-    void* p = nullptr;
-    void* hd = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes);
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
 struct TxPipe {
     int device = -1;
     hipStream_t compute = nullptr, compute2 = nullptr, copy = nullptr;  // chunks alternate compute streams
     std::vector<hipEvent_t> ev;  // 2 per chunk: inputs landed, kernel done
-    PipeBuf b[8];                // 0-4 the pipeline's (inputs, outputs); 5-7 free for a tail's work
-    PipeHostBuf hin, host;       // input / output staging of small batches
+    DevBuf b[8];                 // 0-4 the pipeline's (inputs, outputs); 5-7 free for a tail's work
+    PinnedBuf hin{true}, host{true};  // input / output staging of small batches (device-mapped)
 };
 // txs [lo, hi) of a host batch (the caller's indexing: offsets, outputs at row i for tx i)
 struct HostTxRange {
@@ -143,13 +150,19 @@ struct HostTxRange {
     // shards' first chunks already fill the GPU beside it) and chunks of one round / share
     int share = 1;
 };
+inline HostTxRange host_range(int suite, const uint8_t* pre, const uint64_t* pre_off, const uint8_t* sig,
+                              const uint64_t* sig_off, uint64_t lo, uint64_t hi, uint8_t* txhash32, uint8_t* sender20,
+                              uint8_t* status) {
+    return HostTxRange{suite, pre, pre_off, sig, sig_off, lo, hi, txhash32, sender20, status, 1};
+}
 // queued on p.compute after every chunk's kernel, before the last download: d_hash = the range's
 // (hi - lo) x 32 tx hashes on the device
 using PipeTail = std::function<int(TxPipe& p, const uint8_t* d_hash, std::string& msg)>;
 TxPipe* tx_pipe_acquire(int device);  // nullptr on a HIP failure; the calling thread's device is kept
 void tx_pipe_release(TxPipe* p);
 uint64_t tx_pipe_chunk(uint64_t m, int share = 1);
-// on the calling thread's current device == p.device; returns after every output is in host memory
+// on the calling thread's current device == p.device; returns after every output is in host memory, or,
+// with an error, after everything it queued has finished (a StreamDrain over the pipe's streams)
 int tx_pipeline(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::string& msg);
 
 // tars_kernels.hip

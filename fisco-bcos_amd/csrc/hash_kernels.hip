@@ -681,13 +681,9 @@ static uint32_t* fused_counter_slot(hipStream_t st) {
                              kFusedSlots * kFusedPools, dev);
             return nullptr;
         }
-        int prev = dev;
-        (void)hipGetDevice(&prev);
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
+        DeviceScope on(dev);
         void* b = nullptr;
-        const hipError_t e = hipMalloc(&b, sizeof(uint32_t) * kFusedCounters * kFusedSlots);
-        if (prev != dev) (void)hipSetDevice(prev);
-        if (e != hipSuccess) {
+        if (on.err != hipSuccess || hipMalloc(&b, sizeof(uint32_t) * kFusedCounters * kFusedSlots) != hipSuccess) {
             (void)hipGetLastError();
             return nullptr;
         }

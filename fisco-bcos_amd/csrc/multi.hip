@@ -29,28 +29,12 @@ using namespace bcosgpu;
 
 namespace {
 
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 // a shard's stream and grow-only device buffers; its mutex is held by the call that uses it
 struct ShardCtx {
     std::mutex mu;
     int device = 0;
     hipStream_t stream = nullptr;
-    Buf b[10];
+    DevBuf b[10];
 };
 
 std::mutex g_mmu;
@@ -66,33 +50,6 @@ ShardCtx* shard_ctx(int device, int slot) {
     }
     return c;
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            (void)hipGetLastError();
-            prev = -1;
-        }
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-std::string hip_msg(hipError_t e, const char* what) { return std::string(what) + ": " + hipGetErrorString(e); }
-
-#define SHARD_HIP(call)                                  \
-    do {                                                 \
-        const hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) {                          \
-            msg = hip_msg(e_, #call);                    \
-            return BCOSGPU_E_HIP;                        \
-        }                                                \
-    } while (0)
 
 int check_set(const int* devices, int ndev) {
     if (!devices || ndev < 1 || ndev > 64) return api_set_err(BCOSGPU_E_ARG, "device list: 1 to 64 entries");
@@ -122,7 +79,9 @@ std::vector<std::unique_lock<std::mutex>> lock_all(std::vector<ShardCtx*> cs) {
 }
 
 // f(k, msg) for every shard, shards 1.. on their own host threads; the first failing shard's code,
-// with its message set on the calling thread
+// with its message set on the calling thread.  Every shard thread is joined before the return and every
+// shard drains its own streams before it returns an error (StreamDrain here, tx_pipeline's own), so a
+// failing device-set call returns with every device of the set idle.
 template <class F>
 int run_shards(int ndev, F&& f) {
     std::vector<int> rc(ndev, 0);
@@ -206,7 +165,7 @@ void enable_peers(const int* devices, int ndev) {
         g_peer_done.push_back(pr);
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, pr.first, pr.second) == hipSuccess && can && pr.first != pr.second) {
-            DeviceGuard dg(pr.first);
+            DeviceScope dg(pr.first);
             (void)hipDeviceEnablePeerAccess(pr.second, 0);
         }
         (void)hipGetLastError();
@@ -224,14 +183,15 @@ int gather_root(const int* devices, int ndev, const Plan& p, const std::vector<c
                 int width, ShardCtx* r, uint8_t* root32) {
     std::string msg;
     const int rc = [&]() -> int {
-        DeviceGuard dg(r->device);
-        SHARD_HIP(dg.err);
-        SHARD_HIP(ensure_stream(r));
+        DeviceScope dg(r->device);
+        HIP_TRY(dg.err);
+        HIP_TRY(ensure_stream(r));
         uint64_t total = 0;
         for (int k = 0; k < ndev; ++k) total += p.count(k);
-        SHARD_HIP(r->b[0].ensure(total * 32));
-        SHARD_HIP(r->b[1].ensure((merkle_size(total, width) + 1) * 32));
-        SHARD_HIP(r->b[2].ensure(32));
+        HIP_TRY(r->b[0].ensure(total * 32));
+        HIP_TRY(r->b[1].ensure((merkle_size(total, width) + 1) * 32));
+        HIP_TRY(r->b[2].ensure(32));
+        StreamDrain drain(r->stream);
         const bool peer_all = force_peer();
         uint64_t at = 0;
         for (int k = 0; k < ndev; ++k) {
@@ -239,9 +199,9 @@ int gather_root(const int* devices, int ndev, const Plan& p, const std::vector<c
             if (!m) continue;
             uint8_t* dst = r->b[0].as<uint8_t>() + 32 * at;
             if (devices[k] == r->device && !peer_all)
-                SHARD_HIP(hipMemcpyAsync(dst, frontier[k], 32 * m, hipMemcpyDeviceToDevice, r->stream));
+                HIP_TRY(hipMemcpyAsync(dst, frontier[k], 32 * m, hipMemcpyDeviceToDevice, r->stream));
             else
-                SHARD_HIP(hipMemcpyPeerAsync(dst, r->device, frontier[k], devices[k], 32 * m, r->stream));
+                HIP_TRY(hipMemcpyPeerAsync(dst, r->device, frontier[k], devices[k], 32 * m, r->stream));
             at += m;
         }
         const int lrc = launch_merkle(hasher, width, r->b[0].as<uint8_t>(), total, r->b[1].as<uint8_t>(),
@@ -250,8 +210,9 @@ int gather_root(const int* devices, int ndev, const Plan& p, const std::vector<c
             msg = hip_msg(hipGetLastError(), "merkle top levels launch");
             return lrc;
         }
-        SHARD_HIP(hipMemcpyAsync(root32, r->b[2].p, 32, hipMemcpyDeviceToHost, r->stream));
-        SHARD_HIP(hipStreamSynchronize(r->stream));
+        HIP_TRY(hipMemcpyAsync(root32, r->b[2].p, 32, hipMemcpyDeviceToHost, r->stream));
+        HIP_TRY(hipStreamSynchronize(r->stream));
+        drain.dismiss();
         return 0;
     }();
     return rc ? api_set_err(rc, msg) : 0;
@@ -264,16 +225,9 @@ int sig_multi(const int* devices, int ndev, int kind, size_t n, const uint8_t* h
     return run_shards(ndev, [&](int k, std::string& msg) -> int {
         const uint64_t lo = p.lo[k], m = p.hi[k] - p.lo[k];
         if (!m) return 0;
-        SigJob job;
-        job.kind = kind;
-        job.n = m;
-        job.hash32 = hash32 + 32 * lo;
-        job.sig = sig + sig_stride * lo;
-        job.sig_stride = sig_stride;
-        job.pub64 = pub64 ? pub64 + 64 * lo : nullptr;
-        job.out_pub64 = out_pub64 ? out_pub64 + 64 * lo : nullptr;
-        job.out_addr20 = out_addr20 ? out_addr20 + 20 * lo : nullptr;
-        job.out_ok = ok + lo;
+        SigJob job = sig_job(kind, m, hash32 + 32 * lo, sig + sig_stride * lo, sig_stride,
+                             pub64 ? pub64 + 64 * lo : nullptr, out_pub64 ? out_pub64 + 64 * lo : nullptr,
+                             out_addr20 ? out_addr20 + 20 * lo : nullptr, ok + lo);
         const int rc = coalesced_run(devices[k], job);
         if (rc) msg = job.err;
         return rc;
@@ -304,28 +258,11 @@ int shards_on_device(const int* devices, int ndev, int k, const std::function<bo
     return n;
 }
 
-HostTxRange host_range(int suite, const uint8_t* pre, const uint64_t* pre_off, const uint8_t* sig,
-                       const uint64_t* sig_off, uint64_t lo, uint64_t hi, uint8_t* txhash32, uint8_t* sender20,
-                       uint8_t* status) {
-    HostTxRange t;
-    t.suite = suite;
-    t.pre = pre;
-    t.pre_off = pre_off;
-    t.sig = sig;
-    t.sig_off = sig_off;
-    t.lo = lo;
-    t.hi = hi;
-    t.txhash32 = txhash32;
-    t.sender20 = sender20;
-    t.status = status;
-    return t;
-}
-
 int tx_multi(const int* devices, int ndev, int suite, const uint8_t* pre, const uint64_t* pre_off, const uint8_t* sig,
              const uint64_t* sig_off, size_t n, int width, uint8_t* txhash32, uint8_t* sender20, uint8_t* status,
              uint8_t* root32) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return api_set_err(BCOSGPU_E_ARG, "bad suite");
-    if (root32 && (width < 2 || width > 64)) return api_set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_suite(suite)) return rc;
+    if (root32 && check_width(width)) return BCOSGPU_E_ARG;
     if (n == 0) {  // BlockImpl.h:114-119: a block without transactions has the zero root
         if (root32) std::memset(root32, 0, 32);
         return check_set(devices, ndev);
@@ -348,8 +285,8 @@ int tx_multi(const int* devices, int ndev, int suite, const uint8_t* pre, const 
         const uint64_t lo = p.lo[k], hi = p.hi[k], m = hi - lo;
         if (!m) return 0;
         TxPipe& c = *pipes.p[k];
-        DeviceGuard dg(c.device);
-        SHARD_HIP(dg.err);
+        DeviceScope dg(c.device);
+        HIP_TRY(dg.err);
         // the shard's level-L frontier (or its hashes, L = 0), queued behind the last chunk's kernel
         PipeTail tail = [&](TxPipe& q, const uint8_t* d_hash, std::string& m2) -> int {
             if (!root32) return 0;
@@ -382,8 +319,8 @@ int tx_multi(const int* devices, int ndev, int suite, const uint8_t* pre, const 
 int blocks_multi(const int* devices, int ndev, int suite, const uint8_t* pre, const uint64_t* pre_off, const uint8_t* sig,
                  const uint64_t* sig_off, const uint64_t* block_off, size_t nblocks, int width, uint8_t* txhash32,
                  uint8_t* sender20, uint8_t* status, uint8_t* roots32) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return api_set_err(BCOSGPU_E_ARG, "bad suite");
-    if (width < 2 || width > 64) return api_set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_suite(suite)) return rc;
+    if (int rc = check_width(width)) return rc;
     if (nblocks == 0) return check_set(devices, ndev);
     if (!block_off || !roots32) return api_set_err(BCOSGPU_E_ARG, "null pointer");
     if (block_off[0] != 0) return api_set_err(BCOSGPU_E_ARG, "block_off[0] must be 0");
@@ -417,12 +354,12 @@ int blocks_multi(const int* devices, int ndev, int suite, const uint8_t* pre, co
             return 0;
         }
         TxPipe& c = *pipes.p[k];
-        DeviceGuard dg(c.device);
-        SHARD_HIP(dg.err);
+        DeviceScope dg(c.device);
+        HIP_TRY(dg.err);
         std::vector<uint64_t> boff(nb + 1);
         for (size_t b = 0; b <= nb; ++b) boff[b] = block_off[b0 + b] - lo;
-        SHARD_HIP(c.b[5].ensure(merkle_roots_work_bytes(m, nb, width)));
-        SHARD_HIP(c.b[6].ensure(nb * 32));
+        HIP_TRY(c.b[5].ensure(merkle_roots_work_bytes(m, nb, width)));
+        HIP_TRY(c.b[6].ensure(nb * 32));
         PipeTail tail = [&](TxPipe& q, const uint8_t* d_hash, std::string& m2) -> int {
             const int rrc = launch_merkle_roots_batch(hasher, width, d_hash, boff.data(), nb, q.b[5].as<uint8_t>(),
                                                       q.b[6].as<uint8_t>(), q.compute);
@@ -433,8 +370,10 @@ int blocks_multi(const int* devices, int ndev, int suite, const uint8_t* pre, co
         r.share = shards_on_device(devices, ndev, k, [&](int j) { return block_off[bl[j + 1]] > block_off[bl[j]]; });
         const int rc = tx_pipeline(c, r, tail, msg);
         if (rc) return rc;
-        SHARD_HIP(hipMemcpyAsync(roots32 + 32 * b0, c.b[6].p, nb * 32, hipMemcpyDeviceToHost, c.copy));
-        SHARD_HIP(hipStreamSynchronize(c.copy));
+        StreamDrain drain(c.copy);
+        HIP_TRY(hipMemcpyAsync(roots32 + 32 * b0, c.b[6].p, nb * 32, hipMemcpyDeviceToHost, c.copy));
+        HIP_TRY(hipStreamSynchronize(c.copy));
+        drain.dismiss();
         return 0;
     });
 }
@@ -461,8 +400,8 @@ int bcosgpu_sm2_verify_batch_multi(const int* devices, int ndev, const uint8_t* 
 
 int bcosgpu_verify_batch_multi(const int* devices, int ndev, int suite, const uint8_t* pub64, const uint8_t* hash32,
                                const uint8_t* sig, size_t sig_stride, size_t n, uint8_t* ok) {
-    if (suite != BCOSGPU_SUITE_SECP256K1 && suite != BCOSGPU_SUITE_SM2) return api_set_err(BCOSGPU_E_ARG, "bad suite");
-    if (sig_stride < 64 || sig_stride > 0xFFFFFFFFull) return api_set_err(BCOSGPU_E_ARG, "signature stride must be >= 64");
+    if (int rc = check_suite(suite)) return rc;
+    if (int rc = check_stride(sig_stride)) return rc;
     if (n == 0) return check_set(devices, ndev);
     if (!pub64 || !hash32 || !sig || !ok) return api_set_err(BCOSGPU_E_ARG, "null pointer");
     return sig_multi(devices, ndev, suite == BCOSGPU_SUITE_SM2 ? kSigJobVerifySM2 : kSigJobVerifyK1, n, hash32, sig,
@@ -491,8 +430,8 @@ int bcosgpu_blocks_verify_multi(const int* devices, int ndev, int suite, const u
 
 int bcosgpu_merkle_root_multi(const int* devices, int ndev, int hasher, int width, const uint8_t* leaves32, size_t n,
                               uint8_t* root32) {
-    if (hasher != BCOSGPU_KECCAK256 && hasher != BCOSGPU_SM3) return api_set_err(BCOSGPU_E_ARG, "bad hasher");
-    if (width < 2 || width > 64) return api_set_err(BCOSGPU_E_ARG, "width must be in [2, 64]");
+    if (int rc = check_hasher(hasher)) return rc;
+    if (int rc = check_width(width)) return rc;
     if (n == 0) return api_set_err(BCOSGPU_E_EMPTY, "Empty input");  // Merkle.h:172-175
     if (!leaves32 || !root32) return api_set_err(BCOSGPU_E_ARG, "null pointer");
     if (int rc = check_set(devices, ndev)) return rc;
@@ -512,14 +451,15 @@ int bcosgpu_merkle_root_multi(const int* devices, int ndev, int hasher, int widt
         const uint64_t lo = p.lo[k], m = p.hi[k] - p.lo[k];
         if (!m) return 0;
         ShardCtx* c = ctx[k];
-        DeviceGuard dg(c->device);
-        SHARD_HIP(dg.err);
-        SHARD_HIP(ensure_stream(c));
-        SHARD_HIP(c->b[0].ensure(m * 32));
-        SHARD_HIP(hipMemcpyAsync(c->b[0].p, leaves32 + 32 * lo, m * 32, hipMemcpyHostToDevice, c->stream));
+        DeviceScope dg(c->device);
+        HIP_TRY(dg.err);
+        HIP_TRY(ensure_stream(c));
+        HIP_TRY(c->b[0].ensure(m * 32));
+        StreamDrain drain(c->stream);
+        HIP_TRY(hipMemcpyAsync(c->b[0].p, leaves32 + 32 * lo, m * 32, hipMemcpyHostToDevice, c->stream));
         if (p.levels > 0) {
-            SHARD_HIP(c->b[7].ensure(64 * ((m + width - 1) / width)));
-            SHARD_HIP(c->b[8].ensure(32 * p.count(k)));
+            HIP_TRY(c->b[7].ensure(64 * ((m + width - 1) / width)));
+            HIP_TRY(c->b[8].ensure(32 * p.count(k)));
             const int lrc = launch_merkle_levels(hasher, width, c->b[0].as<uint8_t>(), m, p.levels,
                                                  c->b[7].as<uint8_t>(), c->b[8].as<uint8_t>(), c->stream);
             if (lrc) {
@@ -530,7 +470,8 @@ int bcosgpu_merkle_root_multi(const int* devices, int ndev, int hasher, int widt
         } else {
             frontier[k] = c->b[0].as<uint8_t>();
         }
-        SHARD_HIP(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drain.dismiss();
         return 0;
     });
     if (rc) return rc;

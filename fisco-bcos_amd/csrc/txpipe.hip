@@ -35,49 +35,10 @@
 
 namespace bcosgpu {
 
-hipError_t PipeBuf::ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = bytes < 4096 ? 4096 : bytes + bytes / 4;
-    const hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
-hipError_t PipeHostBuf::ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = hd = nullptr;
-    cap = 0;
-    const size_t want = bytes < 65536 ? 65536 : bytes + bytes / 4;
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocMapped);
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&hd, p, 0);
-    if (e == hipSuccess) cap = want;
-    return e;
-}
-
 namespace {
 
 std::mutex g_pool_mu;
 std::vector<std::vector<TxPipe*>> g_free;  // per device; pipes are never freed (no teardown races)
-
-struct DevGuard {
-    int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) {
-            (void)hipGetLastError();
-            prev = -1;
-        }
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 hipError_t ensure_events(TxPipe& p, size_t need) {
     while (p.ev.size() < need) {
@@ -88,15 +49,6 @@ hipError_t ensure_events(TxPipe& p, size_t need) {
     }
     return hipSuccess;
 }
-
-#define PIPE_HIP(call)                                               \
-    do {                                                             \
-        const hipError_t e_ = (call);                                \
-        if (e_ != hipSuccess) {                                      \
-            msg = std::string(#call) + ": " + hipGetErrorString(e_); \
-            return BCOSGPU_E_HIP;                                    \
-        }                                                            \
-    } while (0)
 
 }  // namespace
 
@@ -109,16 +61,21 @@ TxPipe* tx_pipe_acquire(int device) {
             return p;
         }
     }
-    DevGuard dg(device);
-    if (dg.err != hipSuccess) return nullptr;
+    DeviceScope on(device);
+    if (on.err != hipSuccess) return nullptr;
     TxPipe* p = new TxPipe();
     p->device = device;
-    if (hipStreamCreateWithFlags(&p->compute, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&p->compute2, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&p->copy, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;  // (a pipe without streams is dropped; the caller reports the failure)
-    }
+    hipStream_t* const streams[3] = {&p->compute, &p->compute2, &p->copy};
+    for (hipStream_t* s : streams)
+        if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) {
+            // a pipe without all its streams is dropped with the ones it got; the caller reports the failure
+            *s = nullptr;
+            for (hipStream_t* made : streams)
+                if (*made) (void)hipStreamDestroy(*made);
+            delete p;
+            (void)hipGetLastError();
+            return nullptr;
+        }
     return p;
 }
 
@@ -233,10 +190,10 @@ int tx_small(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::string&
     const uint64_t pb = t.pre_off[lo], pbytes = t.pre_off[hi] - pb;
     const uint64_t sb = t.sig_off[lo], sbytes = t.sig_off[hi] - sb;
     const uint64_t spo = (pbytes + sbytes + 15) & ~7ull, sso = spo + 8 * (m + 1), total = sso + 8 * (m + 1);
-    PIPE_HIP(p.b[0].ensure(total));
-    PIPE_HIP(p.b[4].ensure(53 * m + 8));
-    PIPE_HIP(p.hin.ensure(total));
-    PIPE_HIP(p.host.ensure(53 * m));
+    HIP_TRY(p.b[0].ensure(total));
+    HIP_TRY(p.b[4].ensure(53 * m + 8));
+    HIP_TRY(p.hin.ensure(total));
+    HIP_TRY(p.host.ensure(53 * m));
     uint8_t* h = p.hin.as<uint8_t>();
     uint8_t* d = p.b[0].as<uint8_t>();
     hipStream_t st = p.compute;
@@ -263,7 +220,8 @@ int tx_small(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::string&
         msg = "offsets must be non-decreasing";
         return BCOSGPU_E_ARG;
     }
-    PIPE_HIP(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
+    StreamDrain drain(st);  // (the tail queues on p.compute too: engine.h)
+    HIP_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
     // without a tail the kernel writes its outputs straight into the mapped pinned buffer (no D2H copy and
     // no second wait on the copy engine); a tail reads the hashes on the device.  BCOSGPU_PIPE_ZCOUT=0
     // keeps the device outputs and one D2H (A/B hook, read once)
@@ -283,8 +241,9 @@ int tx_small(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::string&
     if (tail)
         if (int rc = tail(p, d_out, msg)) return rc;
     uint8_t* o = p.host.as<uint8_t>();
-    if (!zc) PIPE_HIP(hipMemcpyAsync(o, d_out, 53 * m, hipMemcpyDeviceToHost, st));
-    PIPE_HIP(hipStreamSynchronize(st));
+    if (!zc) HIP_TRY(hipMemcpyAsync(o, d_out, 53 * m, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drain.dismiss();
     const CopySeg outs[3] = {{t.txhash32 + 32 * lo, o, 32 * m}, {t.sender20 + 20 * lo, o + 32 * m, 20 * m},
                              {t.status + lo, o + 52 * m, m}};
     HostPool::get().run([&](int part, int parts) { copy_range(outs, 3, 53 * m * part / parts, 53 * m * (part + 1) / parts); },
@@ -310,11 +269,11 @@ int tx_pipeline(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::stri
     const uint64_t pb = t.pre_off[lo], pbytes = t.pre_off[hi] - pb;
     const uint64_t sb = t.sig_off[lo], sbytes = t.sig_off[hi] - sb;
     // outputs contiguous: txhash [m][32] | sender [m][20] | status [m]  (sender stays 4-byte aligned)
-    PIPE_HIP(p.b[0].ensure(pbytes + 8));
-    PIPE_HIP(p.b[1].ensure((m + 1) * 8));
-    PIPE_HIP(p.b[2].ensure(sbytes + 8));
-    PIPE_HIP(p.b[3].ensure((m + 1) * 8));
-    PIPE_HIP(p.b[4].ensure(53 * m + 8));
+    HIP_TRY(p.b[0].ensure(pbytes + 8));
+    HIP_TRY(p.b[1].ensure((m + 1) * 8));
+    HIP_TRY(p.b[2].ensure(sbytes + 8));
+    HIP_TRY(p.b[3].ensure((m + 1) * 8));
+    HIP_TRY(p.b[4].ensure(53 * m + 8));
     // chunk boundaries: a quarter-round head chunk first (its upload is the pipeline's exposed start; its
     // kernel is less efficient, but the next chunk's kernel fills the rest of the GPU beside it on the
     // other compute stream), then whole rounds.  Not for a shard sharing its device with another shard of
@@ -339,7 +298,7 @@ int tx_pipeline(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::stri
         while (cb.back() < m) cb.push_back(std::min(m, cb.back() + chunk));
     }
     const uint64_t nchunks = cb.size() - 1;
-    PIPE_HIP(ensure_events(p, 2 * nchunks));
+    HIP_TRY(ensure_events(p, 2 * nchunks));
     // device views of the whole range: the byte buffers shifted back by the range's first offset, so the
     // caller's offsets index them directly
     const uint8_t* d_pre = p.b[0].as<uint8_t>() - pb;
@@ -351,14 +310,18 @@ int tx_pipeline(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::stri
     hipStream_t cs[2] = {p.compute, p.compute2};
     if (const char* e = std::getenv("BCOSGPU_PIPE_STREAMS"))  // A/B hook: 1 = every chunk on one stream
         if (e[0] == '1') cs[1] = p.compute;
-    auto drain = [&](uint64_t k) -> int {  // the large path: chunk k's outputs once its kernel is done
+    auto fetch = [&](uint64_t k) -> int {  // the large path: chunk k's outputs once its kernel is done
         const uint64_t a = cb[k], e = cb[k + 1], c = e - a;
-        PIPE_HIP(hipEventSynchronize(p.ev[2 * k + 1]));
-        PIPE_HIP(hipMemcpyAsync(t.txhash32 + 32 * (lo + a), d_hash + 32 * a, 32 * c, hipMemcpyDeviceToHost, p.copy));
-        PIPE_HIP(hipMemcpyAsync(t.sender20 + 20 * (lo + a), d_snd + 20 * a, 20 * c, hipMemcpyDeviceToHost, p.copy));
-        PIPE_HIP(hipMemcpyAsync(t.status + lo + a, d_st + a, c, hipMemcpyDeviceToHost, p.copy));
+        HIP_TRY(hipEventSynchronize(p.ev[2 * k + 1]));
+        HIP_TRY(hipMemcpyAsync(t.txhash32 + 32 * (lo + a), d_hash + 32 * a, 32 * c, hipMemcpyDeviceToHost, p.copy));
+        HIP_TRY(hipMemcpyAsync(t.sender20 + 20 * (lo + a), d_snd + 20 * a, 20 * c, hipMemcpyDeviceToHost, p.copy));
+        HIP_TRY(hipMemcpyAsync(t.status + lo + a, d_st + a, c, hipMemcpyDeviceToHost, p.copy));
         return 0;
     };
+    // from here on every return first waits for the three streams: an error (bad offsets in a later chunk,
+    // a failed copy, launch or tail) returns with the chunks already launched finished, the caller's arrays
+    // no longer written and the pipe idle for its next user
+    StreamDrain drain(p.compute, p.compute2, p.copy);
     for (uint64_t k = 0; k < nchunks; ++k) {
         const uint64_t a = cb[k], e = cb[k + 1], c = e - a;
         const uint64_t ga = lo + a, ge = lo + e;  // the chunk in the caller's indexing
@@ -366,9 +329,6 @@ int tx_pipeline(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::stri
             if (t.pre_off[i + 1] < t.pre_off[i] || t.sig_off[i + 1] < t.sig_off[i] ||
                 t.pre_off[i + 1] - t.pre_off[i] > 0xFFFFFFFFull || t.pre_off[i + 1] > t.pre_off[hi] ||
                 t.sig_off[i + 1] > t.sig_off[hi]) {
-                (void)hipStreamSynchronize(cs[0]);  // the chunks already launched finish before the error returns
-                (void)hipStreamSynchronize(cs[1]);
-                (void)hipStreamSynchronize(p.copy);
                 msg = "offsets must be non-decreasing";
                 return BCOSGPU_E_ARG;
             }
@@ -376,39 +336,40 @@ int tx_pipeline(TxPipe& p, const HostTxRange& t, const PipeTail& tail, std::stri
         hipStream_t st = cs[k & 1];
         // pageable copies straight from the caller (they return once their data has moved)
         if (p1 > p0)
-            PIPE_HIP(hipMemcpyAsync(p.b[0].as<uint8_t>() + (p0 - pb), t.pre + p0, p1 - p0, hipMemcpyHostToDevice,
-                                    p.copy));
+            HIP_TRY(hipMemcpyAsync(p.b[0].as<uint8_t>() + (p0 - pb), t.pre + p0, p1 - p0, hipMemcpyHostToDevice,
+                                   p.copy));
         if (s1 > s0)
-            PIPE_HIP(hipMemcpyAsync(p.b[2].as<uint8_t>() + (s0 - sb), t.sig + s0, s1 - s0, hipMemcpyHostToDevice,
-                                    p.copy));
-        PIPE_HIP(hipMemcpyAsync(d_po + a, t.pre_off + ga, (c + 1) * 8, hipMemcpyHostToDevice, p.copy));
-        PIPE_HIP(hipMemcpyAsync(d_so + a, t.sig_off + ga, (c + 1) * 8, hipMemcpyHostToDevice, p.copy));
-        PIPE_HIP(hipEventRecord(p.ev[2 * k], p.copy));
-        PIPE_HIP(hipStreamWaitEvent(st, p.ev[2 * k], 0));
+            HIP_TRY(hipMemcpyAsync(p.b[2].as<uint8_t>() + (s0 - sb), t.sig + s0, s1 - s0, hipMemcpyHostToDevice,
+                                   p.copy));
+        HIP_TRY(hipMemcpyAsync(d_po + a, t.pre_off + ga, (c + 1) * 8, hipMemcpyHostToDevice, p.copy));
+        HIP_TRY(hipMemcpyAsync(d_so + a, t.sig_off + ga, (c + 1) * 8, hipMemcpyHostToDevice, p.copy));
+        HIP_TRY(hipEventRecord(p.ev[2 * k], p.copy));
+        HIP_TRY(hipStreamWaitEvent(st, p.ev[2 * k], 0));
         const int lrc = launch_tx_verify(t.suite, d_pre, d_po + a, d_sig, d_so + a, c, d_hash + 32 * a, d_snd + 20 * a,
                                          d_st + a, st);
         if (lrc) {
             msg = std::string("tx verify launch: ") + hipGetErrorString(hipGetLastError());
             return lrc;
         }
-        PIPE_HIP(hipEventRecord(p.ev[2 * k + 1], st));
+        HIP_TRY(hipEventRecord(p.ev[2 * k + 1], st));
         if (k + 1 == nchunks) {
             // compute stream 0 joins the other stream's last chunk, then the follow-on kernels over the
             // whole range's hashes (roots, frontier)
             if (nchunks >= 2) {
                 const uint64_t j = (k & 1) ? k : k - 1;  // the last chunk that ran on stream 1
-                PIPE_HIP(hipStreamWaitEvent(cs[0], p.ev[2 * j + 1], 0));
+                HIP_TRY(hipStreamWaitEvent(cs[0], p.ev[2 * j + 1], 0));
             }
             if (tail)
                 if (int rc = tail(p, d_hash, msg)) return rc;
         }
         if (k >= 1)
-            if (int rc = drain(k - 1)) return rc;
+            if (int rc = fetch(k - 1)) return rc;
     }
-    if (int rc = drain(nchunks - 1)) return rc;
-    PIPE_HIP(hipStreamSynchronize(p.copy));
-    PIPE_HIP(hipStreamSynchronize(cs[0]));
-    PIPE_HIP(hipStreamSynchronize(cs[1]));
+    if (int rc = fetch(nchunks - 1)) return rc;
+    HIP_TRY(hipStreamSynchronize(p.copy));
+    HIP_TRY(hipStreamSynchronize(cs[0]));
+    HIP_TRY(hipStreamSynchronize(cs[1]));
+    drain.dismiss();
     return 0;
 }
 

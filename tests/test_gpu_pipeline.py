@@ -127,25 +127,54 @@ def test_pipeline_concurrent_callers(gpu, oracle):
 
 
 def test_pipeline_rejects_bad_offsets_mid_batch(gpu, oracle, monkeypatch):
-    """Offsets are checked chunk by chunk inside the pipeline: a decreasing offset in the third chunk is
+    """Offsets are checked chunk by chunk inside the pipeline: a decreasing offset in a later chunk is
     BCOSGPU_E_ARG (after the chunks already launched have drained), for the single-device and the
-    device-set calls; the same pipelines then verify a good batch correctly."""
+    device-set calls -- at tx 250 (shard 0 of [0, 0] fails) and at tx 700 (shard 1, txs 452-899, fails
+    while shard 0 completes); a 64-tx batch on the small path is refused before anything is launched.  After
+    the error return nothing writes the caller's arrays any more (the canary).  The same pipelines then
+    verify good batches correctly."""
+    import torch
     from bcos_gpu import synth, tx
-    from bcos_gpu._lib import E_ARG, BcosGpuError
+    from bcos_gpu._lib import E_ARG, BcosGpuError, lib
+    from bcos_gpu.crypto import _ptr
     b = synth.make_batch(0, 900, seed=0xBAD0)
     pre, po, sg, so = _host(b)
     s = gpu.secp256k1_suite()
+    wh, ws, wst = oracle.tx_verify_packed(0, pre, po, sg, so, nthreads=8)
+
+    def broken(off, at):
+        bad = off.copy()
+        bad[at] = bad[at - 1] - 1
+        return bad
     monkeypatch.setenv("BCOSGPU_PIPE_CHUNK", "100")
-    bad_po, bad_so = po.copy(), so.copy()
-    bad_po[250] = bad_po[249] - 1
-    bad_so[250] = bad_so[249] - 1
-    for args in ((pre, bad_po, sg, so), (pre, po, sg, bad_so)):
+    for at in (250, 700):
+        for args in ((pre, broken(po, at), sg, so), (pre, po, sg, broken(so, at))):
+            with pytest.raises(BcosGpuError) as e:
+                tx.verify_packed(s, *args)
+            assert e.value.code == E_ARG
+            with pytest.raises(BcosGpuError) as e:
+                tx.verify_packed_multi([0, 0], s, *args, width=2)
+            assert e.value.code == E_ARG
+    # the canary: the caller's arrays, refilled right after the error return, stay as filled (whatever the
+    # chunks that ran wrote before the return is not asserted)
+    outs = (np.zeros((900, 32), dtype=np.uint8), np.zeros((900, 20), dtype=np.uint8), np.zeros(900, dtype=np.uint8))
+    bad_po = broken(po, 250)
+    rc = lib().bcosgpu_tx_verify_batch(s.suite, _ptr(pre), _ptr(bad_po), _ptr(sg), _ptr(so), 900, *map(_ptr, outs))
+    for a in outs:
+        a.fill(0xA5)
+    torch.cuda.synchronize()
+    assert rc == E_ARG
+    assert all(bool((a == 0xA5).all()) for a in outs)
+    th, snd, st = tx.verify_packed(s, pre, po, sg, so)
+    assert np.array_equal(th, wh) and np.array_equal(snd, ws) and np.array_equal(st, wst)
+    th, snd, st, root = tx.verify_packed_multi([0, 0], s, pre, po, sg, so, width=2)
+    assert np.array_equal(th, wh) and np.array_equal(snd, ws) and np.array_equal(st, wst)
+    assert root == oracle.merkle(oracle.KECCAK256, 2, wh)
+    # the small path (one launch through pinned staging): E_ARG before the launch, then the good 64
+    monkeypatch.delenv("BCOSGPU_PIPE_CHUNK")
+    for args in ((pre, broken(po[:65], 40), sg, so[:65]), (pre, po[:65], sg, broken(so[:65], 40))):
         with pytest.raises(BcosGpuError) as e:
             tx.verify_packed(s, *args)
         assert e.value.code == E_ARG
-        with pytest.raises(BcosGpuError) as e:
-            tx.verify_packed_multi([0, 0], s, *args, width=2)
-        assert e.value.code == E_ARG
-    wh, ws, wst = oracle.tx_verify_packed(0, pre, po, sg, so, nthreads=8)
-    th, snd, st = tx.verify_packed(s, pre, po, sg, so)
-    assert np.array_equal(th, wh) and np.array_equal(snd, ws) and np.array_equal(st, wst)
+    th, snd, st = tx.verify_packed(s, pre, po[:65], sg, so[:65])
+    assert np.array_equal(th, wh[:64]) and np.array_equal(snd, ws[:64]) and np.array_equal(st, wst[:64])
