@@ -35,6 +35,21 @@ def hash_batch(hasher, data, offsets, out, stream=None):
     check(lib().bcosgpu_hash_batch_dev(hasher, _p(data), _p(offsets), n, _p(out), _s(stream)))
 
 
+def state_root_work_size(n):
+    return int(lib().bcosgpu_state_root_work_size(n))
+
+
+def state_root(hasher, block_version, data, off3, kind, work, root, stream=None):
+    """The state root of n packed storage entries (bcosgpu_state_root_dev; the layout of
+    state.pack_state_entries): data uint8[B], off3 int64[3n+1], kind uint8[n], work uint8[>=
+    state_root_work_size(n)], root uint8[32]."""
+    _dev(root)
+    n = kind.numel()
+    assert off3.numel() == 3 * n + 1
+    check(lib().bcosgpu_state_root_dev(hasher, block_version, _p(data), _p(off3), _p(kind), n, _p(work),
+                                       work.numel() * work.element_size(), _p(root), _s(stream)))
+
+
 def merkle_size(n, width):
     return int(lib().bcosgpu_merkle_size(n, width))
 

@@ -379,6 +379,53 @@ int bcosgpu_receipt_roots(int hasher, const bcosgpu_TransactionReceiptData* rece
     return c.finish();
 }
 
+// ------------------------------------------------------------------ state root
+uint64_t bcosgpu_state_root_work_size(size_t n) { return state_root_work_bytes(n); }
+
+int bcosgpu_state_root_dev(int hasher, uint32_t block_version, const uint8_t* d_data, const uint64_t* d_off3,
+                           const uint8_t* d_kind, size_t n, void* d_work, uint64_t work_bytes, uint8_t* d_root32,
+                           void* stream) {
+    if (int rc = check_hasher(hasher)) return rc;
+    if (!d_root32 || (n && (!d_data || !d_off3 || !d_kind || !d_work))) return set_err(BCOSGPU_E_ARG, "null pointer");
+    const int rc = launch_state_root(hasher, block_version, d_data, d_off3, d_kind, n, d_work, work_bytes, d_root32,
+                                     as_stream(stream));
+    if (rc == BCOSGPU_E_ARG) return set_err(rc, "work buffer too small or batch too large");
+    return rc ? hip_err(hipGetLastError(), "state root launch") : 0;
+}
+
+// StateStorage::hash / KeyPageStorage::hash (StateStorage.h:397-431, KeyPageStorage.cpp:351-406): the entries
+// are packed (pack.cpp) straight into pinned staging as off3 | data | kind, one H2D, the fused kernel and its
+// fold, 32 bytes back.
+int bcosgpu_state_root(int hasher, uint32_t block_version, const bcosgpu_StateEntry* entries, size_t n,
+                       uint8_t* root32) {
+    if (int rc = check_hasher(hasher)) return rc;
+    if (!root32 || (n && !entries)) return set_err(BCOSGPU_E_ARG, "null pointer");
+    if (n == 0) {  // no dirty entry: the zero hash (StateStorage.h:399)
+        std::memset(root32, 0, 32);
+        return 0;
+    }
+    WsCall c;
+    if (c.rc) return c.rc;
+    Workspace* w = c.w;
+    const uint64_t bytes = bcosgpu_state_entries_size(entries, n), offb = 8 * (3 * static_cast<uint64_t>(n) + 1);
+    const uint64_t total = offb + bytes + n, work = state_root_work_bytes(n);
+    HIP_OK(w->h[0].ensure(total + 16));
+    uint64_t* off3 = w->h[0].as<uint64_t>();
+    uint8_t* data = reinterpret_cast<uint8_t*>(off3) + offb;
+    if (bcosgpu_pack_state_entries(entries, n, data, bytes, off3, data + bytes))
+        return set_err(BCOSGPU_E_ARG, "bad state entry view (null field with a length, status outside 0..3, or an "
+                                      "entry of 4 GiB or more)");
+    HIP_OK(c.ensure({total + 16, work, 32}));
+    HIP_OK(c.h2d(0, off3, total));
+    const uint8_t* d_data = c.buf(0) + offb;
+    const int rc = launch_state_root(hasher, block_version, d_data, c.buf<uint64_t>(0), d_data + bytes, n, c.buf<void>(1),
+                                     work, c.buf(2), c.stream());
+    if (rc == BCOSGPU_E_ARG) return set_err(rc, "batch too large");
+    if (rc) return hip_err(hipGetLastError(), "state root launch");
+    HIP_OK(c.d2h(root32, 2, 32));
+    return c.finish();
+}
+
 // ------------------------------------------------------------------ Merkle proofs
 uint64_t bcosgpu_merkle_proof_stride(uint64_t n, int width) {
     if (width < 2 || width > 64 || n == 0) return 0;

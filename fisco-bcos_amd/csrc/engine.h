@@ -48,6 +48,12 @@ uint64_t merkle_levels(uint64_t n, int width);
 // the output vector -> the packed vector<bytes> layout (4-byte count records)
 int launch_merkle_compact(const uint8_t* d_tree, uint64_t n, int width, uint8_t* d_out, hipStream_t st);
 
+// state_kernels.hip: the fused hash-and-XOR state root over bcosgpu_pack_state_entries' layout
+uint64_t state_root_work_bytes(uint64_t n);
+int launch_state_root(int hasher, uint32_t block_version, const uint8_t* d_data, const uint64_t* d_off3,
+                      const uint8_t* d_kind, uint64_t n, void* d_work, uint64_t work_bytes, uint8_t* d_root,
+                      hipStream_t st);
+
 // ecc_tables.hip, ecc_sig.hip, ecc_txv.hip (the ECC kernels: tables, signing, verify / recover launchers)
 int ecc_init_tables(int device, int small_tables);
 void set_tx_kernel_policy(int split, int occ, int coop, int f26);

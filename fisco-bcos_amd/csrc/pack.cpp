@@ -95,6 +95,25 @@ void pack_receipt(const bcosgpu_TransactionReceiptData& r, uint8_t* o) {
     put(o, w, 8);
 }
 
+// ---- state entries: table || key || value, the slices StateStorage::hash (StateStorage.h:397-431) and
+// Entry::hash (Entry.h:229-309) hash.  Only a MODIFIED entry's value is read (Entry.h:244-247, :281-285).
+bool valid(const bcosgpu_StateEntry& e) {
+    if (e.status < BCOSGPU_ENTRY_NORMAL || e.status > BCOSGPU_ENTRY_MODIFIED) return false;
+    if ((!e.table && e.table_len) || (!e.key && e.key_len)) return false;
+    return e.status != BCOSGPU_ENTRY_MODIFIED || e.value || !e.value_len;
+}
+
+size_t state_value_len(const bcosgpu_StateEntry& e) { return e.status == BCOSGPU_ENTRY_MODIFIED ? e.value_len : 0; }
+
+// false when the entry's packed length reaches 2^32 (the kernels' readers take 32-bit lengths)
+bool state_entry_len(const bcosgpu_StateEntry& e, uint64_t* len) {
+    const uint64_t lim = 1ull << 32;
+    const uint64_t t = e.table_len, k = e.key_len, v = state_value_len(e);
+    if (t >= lim || k >= lim || v >= lim || t + k + v >= lim) return false;
+    *len = t + k + v;
+    return true;
+}
+
 // items [0, n) packed by `pack(i, out + offsets[i])` on a pool of std::threads over contiguous ranges
 template <class F>
 void pack_parallel(size_t n, F&& pack) {
@@ -165,6 +184,40 @@ int bcosgpu_pack_receipt_preimages(const bcosgpu_TransactionReceiptData* receipt
     }
     if (offsets[n] > cap || (offsets[n] && !out)) return BCOSGPU_E_ARG;
     pack_parallel(n, [&](size_t i) { pack_receipt(receipts[i], out + offsets[i]); });
+    return BCOSGPU_OK;
+}
+
+uint64_t bcosgpu_state_entries_size(const bcosgpu_StateEntry* entries, size_t n) {
+    if (!entries) return 0;
+    uint64_t s = 0;
+    for (size_t i = 0; i < n; ++i) s += entries[i].table_len + entries[i].key_len + state_value_len(entries[i]);
+    return s;
+}
+
+int bcosgpu_pack_state_entries(const bcosgpu_StateEntry* entries, size_t n, uint8_t* out, uint64_t cap, uint64_t* off3,
+                               uint8_t* kind) {
+    if (n == 0) {
+        if (off3) off3[0] = 0;
+        return BCOSGPU_OK;
+    }
+    if (!entries || !off3 || !kind) return BCOSGPU_E_ARG;
+    off3[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bcosgpu_StateEntry& e = entries[i];
+        uint64_t len;
+        if (!valid(e) || !state_entry_len(e, &len)) return BCOSGPU_E_ARG;
+        off3[3 * i + 1] = off3[3 * i] + e.table_len;
+        off3[3 * i + 2] = off3[3 * i + 1] + e.key_len;
+        off3[3 * i + 3] = off3[3 * i] + len;
+    }
+    if (off3[3 * n] > cap || (off3[3 * n] && !out)) return BCOSGPU_E_ARG;
+    pack_parallel(n, [&](size_t i) {
+        const bcosgpu_StateEntry& e = entries[i];
+        uint8_t* o = put(out + off3[3 * i], e.table, e.table_len);
+        o = put(o, e.key, e.key_len);
+        put(o, e.value, state_value_len(e));
+        kind[i] = static_cast<uint8_t>(static_cast<uint8_t>(e.status) | (e.flags << 4));
+    });
     return BCOSGPU_OK;
 }
 

@@ -340,6 +340,65 @@ void bcosgpu_apply_receipt_data_hashes(const bcosgpu_TransactionReceiptData* rec
 int bcosgpu_receipt_roots(int hasher, const bcosgpu_TransactionReceiptData* receipts, const uint64_t* block_off,
                           size_t nblocks, uint8_t* roots32, uint8_t* hashes32);
 
+/* ---------------------------------------------------------------- state root (StateStorage::hash / KeyPageStorage::hash) */
+/* The third root of a block header (bcos-scheduler/src/BlockExecutive.cpp:1120-1126), from
+ * TransactionExecutor::getHash -> storage->hash(hashImpl) (bcos-executor/src/executor/TransactionExecutor.cpp:1099):
+ * the 256-bit XOR, over the block's dirty storage entries, of each entry's contribution
+ *   StateStorage::hash (bcos-table/src/StateStorage.h:397-431):
+ *       H(table) ^ H(key) ^ Entry::hash(table, key, H, blockVersion)
+ *   KeyPageStorage::hash (bcos-table/src/KeyPageStorage.cpp:351-406), a system-table entry (:385-390): the same
+ *   PageData::hash (bcos-table/src/KeyPageStorage.h:862-893), a page entry: Entry::hash alone at block version
+ *       >= 3.1 (:873-876), H(table) ^ H(key) ^ Entry::hash at 3.0 (:877-881)
+ *   Entry::hash (bcos-framework/bcos-framework/storage/Entry.h:229-309):
+ *       blockVersion >= V3_1_VERSION 0x03010000 (:233): MODIFIED H(table || key || value) (:239-248),
+ *                                                       DELETED H(table || key) (:258-260)
+ *       3.0 (:279-307): MODIFIED H(value) (:281-285), DELETED HashType(0x1) = 31 zero bytes then 0x01
+ *                                                       (:293-295, bcos-utilities/bcos-utilities/FixedBytes.h:171)
+ *       a clean entry (NORMAL, EMPTY) is not dirty and contributes nothing (:269-274, :302-306, StateStorage.h:412)
+ * XOR is exact and commutative: entries may be given in any order. */
+/* Entry::Status (Entry.h) */
+#define BCOSGPU_ENTRY_NORMAL 0
+#define BCOSGPU_ENTRY_DELETED 1
+#define BCOSGPU_ENTRY_EMPTY 2
+#define BCOSGPU_ENTRY_MODIFIED 3
+/* per-entry flag: the entry also contributes H(table) ^ H(key).  Set for every StateStorage entry
+ * (StateStorage.h:414), every KeyPage system-table entry (KeyPageStorage.cpp:386-388) and every KeyPage page
+ * entry when the block version is 3.0 (KeyPageStorage.h:879); not for a page entry from 3.1 on (:875). */
+#define BCOSGPU_STATE_XOR_NAMES 1
+/* A view of one storage entry: pointers into the caller's storage, nothing is copied until packing.  value is
+ * read only when status is MODIFIED. */
+typedef struct {
+    const char* table;     size_t table_len;
+    const char* key;       size_t key_len;
+    const uint8_t* value;  size_t value_len;
+    int8_t status;  /* BCOSGPU_ENTRY_* */
+    uint8_t flags;  /* BCOSGPU_STATE_XOR_NAMES */
+} bcosgpu_StateEntry;
+/* Total packed bytes of n entries (table + key, plus the value of a MODIFIED entry). */
+uint64_t bcosgpu_state_entries_size(const bcosgpu_StateEntry* entries, size_t n);
+/* Packs table || key || value of every entry back to back into out (cap bytes): off3 has 3n+1 entries,
+ * off3[3i], off3[3i+1], off3[3i+2] the starts of entry i's table, key and value and off3[3i+3] its value's end,
+ * so H(table), H(key), H(value), H(table||key) and H(table||key||value) are all contiguous slices; kind[i] =
+ * status | flags << 4.  A DELETED or clean entry packs no value bytes.  Host only, multithreaded for large
+ * batches.  BCOSGPU_E_ARG if cap is too small, a pointer is null with a non-zero length, a status is outside
+ * 0..3, or one entry's packed length reaches 2^32 (the kernels read 32-bit lengths). */
+int bcosgpu_pack_state_entries(const bcosgpu_StateEntry* entries, size_t n, uint8_t* out, uint64_t cap,
+                               uint64_t* off3, uint8_t* kind);
+/* Bytes of d_work (4-byte aligned) for bcosgpu_state_root_dev over n entries. */
+uint64_t bcosgpu_state_root_work_size(size_t n);
+/* The state root of n packed entries (the layout above, in device memory; block_version as in the block header,
+ * e.g. 0x03010000), stream-ordered: a fused hash-and-XOR kernel (no digest is written to memory) whose
+ * workgroups leave 32-byte partials in d_work, the same over the entries of more than 1 KiB it set aside
+ * (listed in d_work, so that long messages share waves), and a fold of the partials into d_root32.  d_work's
+ * earlier contents do not matter.  n == 0 writes the zero hash.  n and every entry's packed length must be
+ * below 2^32. */
+int bcosgpu_state_root_dev(int hasher, uint32_t block_version, const uint8_t* d_data, const uint64_t* d_off3,
+                           const uint8_t* d_kind, size_t n, void* d_work, uint64_t work_bytes, uint8_t* d_root32,
+                           void* stream);
+/* The same from host views: packed into pinned staging, one H2D copy, the kernels, a 32-byte copy back. */
+int bcosgpu_state_root(int hasher, uint32_t block_version, const bcosgpu_StateEntry* entries, size_t n,
+                       uint8_t* root32);
+
 /* ---------------------------------------------------------------- single calls on an explicit device */
 /* One signature per call, for the reference's per-transaction call sites: TxPool's submitter threads
  * (TxPool.h:48-49) -> TxValidator::verify (TxValidator.cpp:56) -> Transaction::verify (Transaction.h:68-82)

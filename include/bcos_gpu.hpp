@@ -255,7 +255,18 @@ inline HashType calculateReceiptRoot(const std::vector<bcosgpu_TransactionReceip
     return calculateReceiptRoots<HASHER>({receipts})[0];
 }
 
-/* EVM ecRecover precompile (bcos-executor/src/vm/Precompiled.cpp:443-482): {true, 32-byte output}
+/* The state root of a block's dirty storage entries -- TransactionExecutor::getHash -> StateStorage::hash
+ * (StateStorage.h:397-431) / KeyPageStorage::hash (KeyPageStorage.cpp:351-406): the XOR of every entry's
+ * Entry::hash (Entry.h:229-309), with H(table) ^ H(key) for the entries flagged BCOSGPU_STATE_XOR_NAMES,
+ * hashed and reduced on the GPU.  No entries, or only clean ones, give the zero hash. */
+template <int HASHER>
+inline HashType calculateStateRoot(const std::vector<bcosgpu_StateEntry>& entries, uint32_t blockVersion) {
+    HashType root{};
+    check(bcosgpu_state_root(HASHER, blockVersion, entries.data(), entries.size(), root.data()));
+    return root;
+}
+
+/* EVM ecRecover precompile(bcos-executor/src/vm/Precompiled.cpp:443-482): {true, 32-byte output}
  * on success, {true, {}} on failure; `in` is read as 128 zero-padded bytes. */
 inline std::pair<bool, bytes> ecRecover(const uint8_t* in, size_t len) {
     alignas(16) uint8_t buf[128] = {0};
