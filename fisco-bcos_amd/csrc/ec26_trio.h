@@ -545,4 +545,62 @@ F26_HD void trio_add(TrioPt& R, const TrioPt& P, const TrioPt& Q, const TrioLane
     R = O;
 }
 
+// The Jacobian representative (X K, Y K l, Z K) of the point (X, Y, Z l), for K = l^2: the scaling by l
+// that leaves l in the Y coordinate only.  The lane-trio kernel maps its chains' sum from E_w to E this way
+// (l = Zc y, K = Zc^2 w): X and Z are then free of the square root y.  In two steps, so that the first can
+// run before y is known: trio_scale_xz gives X K and Z K (and Y K on lanes 1 and 2 of S1, not yet a
+// coordinate), trio_scale_y multiplies that Y K by l.  S: X, Y, Z <= 16; K, l <= 2 -> (1, 1, 1).
+F26_HD void trio_scale_xz(TrioPt& R, const TrioPt& S, const fe26& K, const TrioLane&) {
+    using namespace trio;
+    TrioPt O;
+    mul(O.S1, S.S1, K);                                  // (X K | Y K | Y K)
+    mul(O.Xs, S.Xs, K);
+    mul(O.Zs, S.Zs, K);
+    O.inf = S.inf;
+    R = O;
+}
+F26_HD void trio_scale_y(TrioPt& R, const fe26& l, const TrioLane& T) {
+    using namespace trio;
+    fe26 t;
+    mul(t, R.S1, l);
+    sel(R.S1, T.r0, R.S1, t);                            // (X K | Y K l | Y K l)
+}
+
+// Z3 of trio_add(P, Q) alone (lane 2), from the X and Z coordinates only -- P.S1 and Q.S1 on lane 0, P.Zs
+// and Q.Zs on lane 2 -- in 3 product levels, for a caller whose Y(Q) is not known yet (the lane-trio
+// kernel's last addition, ecc_coop.hip):
+//   L1  Z1Z1 = Z1^2      | Z2Z2 = Z2^2     | Z1 Z2
+//   L2  U2 = X2 Z1Z1     | U1 = X1 Z2Z2    | --
+//   L3  --               | --              | Z1 Z2 H             (H = U2 - U1 on lane 2)
+// The same value as trio_add's Z3 in each of its cases: 2 Z1 Z2 H, Z(Q) for P = infinity, Z(P) for
+// Q = infinity, and for H = 0 the Z of dbl(P) = 2 Y1 Z1 (P.S1 on lane 2 is Y1), which is trio_add's when
+// P = Q; when P = -Q the sum is infinity and its Z is never read.  X, Z <= 16 (both) -> m <= 16.
+F26_HD void trio_add_z(fe26& Z3, const TrioPt& P, const TrioPt& Q, const TrioLane& T) {
+    using namespace trio;
+    fe26 a, b, P1, Q1, o1, P2, o2, u2, u1, h, z;
+    fdpp<kR2>(a, P.Zs);                                  // lane 0: Z1
+    fdpp<kR1>(b, Q.Zs);                                  // lane 1: Z2
+    sel(P1, T.r0, a, b);
+    sel(P1, T.r2, P.Zs, P1);                             // (Z1 | Z2 | Z1)
+    sel(Q1, T.r2, Q.Zs, P1);                             // (Z1 | Z2 | Z2)
+    mul(o1, P1, Q1);                                     // (Z1Z1 | Z2Z2 | Z1 Z2)        m 1
+    fdpp<kL1>(a, P.S1);                                  // lane 1: X1
+    sel(P2, T.r1, a, Q.S1);                              // (X2 | X1 | -)
+    mul(o2, P2, o1);                                     // (U2 | U1 | -)
+    fdpp<kL2>(u2, o2);                                   // lane 0's U2 at lane 2
+    fdpp<kL1>(u1, o2);                                   // lane 1's U1 at lane 2
+    fe26_sub<2>(h, u2, u1);                              // H                            m 3
+    mul(z, o1, h);                                       // lane 2: Z1 Z2 H
+    fe26_mul_int<2>(Z3, z);                              //                              m 2
+    const bool hz = T.r2 && fe26_is_zero(h) && !P.inf && !Q.inf;  // (lanes 0 and 1 hold no H)
+    if (any(hz)) {                                       // P = +-Q (rare)
+        fe26 d;
+        fe26_mul(d, P.S1, P.Zs);                         // lane 2: Y1 Z1
+        fe26_mul_int<2>(d, d);
+        fe26_cmov(Z3, d, hz);
+    }
+    fe26_cmov(Z3, Q.Zs, P.inf);
+    fe26_cmov(Z3, P.Zs, !P.inf && Q.inf);
+}
+
 }  // namespace bcosgpu

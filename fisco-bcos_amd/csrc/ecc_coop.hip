@@ -1006,6 +1006,7 @@ __device__ __forceinline__ void lds_store_fe26(uint32_t (*dst)[64], const fe26& 
 // is trio p / 3 (p = 15 a phantom that mirrors trio 4 and stores nothing).
 // The trio kernel's LDS: Coop26Lds without the wave-pair exchange slots, and the co-Z table (and
 // beta x) kept as canonical fe26 limbs, so a window's lookup is 20 LDS reads and no conversion.
+constexpr int kTrioWords = 31;  // a TrioPt in LDS (trio_store)
 struct Trio26Lds {
     uint32_t tab[8][20][64];          // [entry][x limbs 0..9, y limbs 0..9][tx]
     uint32_t tabphx[8][10][64];       // beta * x
@@ -1019,6 +1020,17 @@ struct Trio26Lds {
     uint32_t rflag[64];
     uint32_t post[3];
     uint32_t invq[2][4];  // phase D: Z^-1 over wave pairs (0, 1) and (2, 3): posted, consumed, d ready
+    // the split square root (BCOSGPU_TRIO_SQRT_SPLIT): the head's live elements and w, raw limbs, from
+    // phase A's wave 2 to phase D's chain-1 waves; and their verdict y^2 = w
+    uint32_t sq[6][10][40];
+    uint32_t yok[64];
+    // with the split root no barrier separates the phases up to phase D's last addition (the chain-1 waves,
+    // which leave phase A first, run ahead and sum the comb partials early), so the hand-offs are flags:
+    // 0 table, k and flags ready (wave 1); 1 + w: wave w's comb partial stored; 5 + p: wave pair p's chain-1
+    // point stored.  The points then cannot reuse the table's LDS: xg holds them ([pair] chain point /
+    // sum S / X3 Y3, [2 + pair] the G part).
+    uint32_t spost[8];
+    uint32_t xg[4][kTrioWords][64];
 };
 // phase D's Z^-1 ring and d (two wave pairs) live in pt, which is free by then
 static_assert(2 * (kInvRing * 4 * 64 + 9 * 64) <= sizeof(Trio26Lds::pt) / 4, "Z^-1 queue exceeds pt");
@@ -1032,7 +1044,6 @@ __device__ __forceinline__ void lds_store_limbs26(uint32_t (*dst)[64], const fe2
 
 // a TrioPt through LDS (phase D of the trio kernel): [S1 limbs, Xs limbs, Zs limbs, inf][lane], the raw
 // limbs (magnitudes travel with the values)
-constexpr int kTrioWords = 31;
 __device__ __forceinline__ void trio_store(uint32_t* buf, const TrioPt& P, int lane) {
 #pragma unroll
     for (int q = 0; q < 10; ++q) {
@@ -1123,11 +1134,32 @@ enum { kRecover = 0, kVerify = 1 };
 #ifndef BCOSGPU_TRIO_INV_SPLIT
 #define BCOSGPU_TRIO_INV_SPLIT 1  // phase-D Z^-1 over wave pairs (0 = the one-wave pipelined loop, A/B)
 #endif
+// The trio kernel's recovery square root y = w^((p+1)/4) cut in two (fe26_sqrt_head / fe26_sqrt_tail): wave 2
+// runs the head in phase A and then takes comb windows like the other waves; the chain-1 waves run the
+// tail in phase D, beside the Z^-1 of the chain-0 waves, whose input does not depend on y.
+// 0: the whole root in phase A (the earlier schedule); 1: cut after x176 (tail 78 S + 4 M; Z^-1 on one
+// wave, its partner being busy); 2: cut after x223 (tail 31 S + 2 M; Z^-1 as BCOSGPU_TRIO_INV_SPLIT says).
+#ifndef BCOSGPU_TRIO_SQRT_SPLIT
+#define BCOSGPU_TRIO_SQRT_SPLIT 1
+#endif
+// with the split root: the first comb window of waves 3, 2 and 1 (wave 0 starts at 0; of the 16 windows of
+// the 16-bit comb, doubled for the 8-bit comb); a wave with no window adds no partial in phase D
+#ifndef BCOSGPU_TRIO_SPLIT_WIN
+#if BCOSGPU_TRIO_SQRT_SPLIT == 2
+#define BCOSGPU_TRIO_SPLIT_WIN 7, 14, 14
+#else
+#define BCOSGPU_TRIO_SPLIT_WIN 7, 13, 16
+#endif
+#endif
 template <bool TRIO, int MODE, class IO>
 __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint32_t* __restrict__ tab, int tab_bits) {
     static_assert(MODE == kRecover || TRIO, "known-key verify runs on the trio kernel only");
     constexpr bool kVer = MODE == kVerify;
     constexpr int TPW = TRIO ? 40 : 64;  // txs per workgroup
+    constexpr bool kSplit = TRIO && !kVer && BCOSGPU_TRIO_SQRT_SPLIT != 0;  // the square root's tail in phase D
+    constexpr int kCut = BCOSGPU_TRIO_SQRT_SPLIT == 2 ? 1 : 0, kLive = fe26_sqrt_live<kCut>();
+    constexpr int kSw[3] = {BCOSGPU_TRIO_SPLIT_WIN};
+    static_assert(0 < kSw[0] && kSw[0] < kSw[1] && kSw[1] <= kSw[2] && kSw[2] <= 16, "comb windows of waves 0, 3, 2, 1");
     __shared__ std::conditional_t<TRIO, Trio26Lds, Coop26Lds> L;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * TPW + lane;
@@ -1140,6 +1172,8 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
         if constexpr (TRIO) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) (&L.invq[0][0])[q] = 0u;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) L.spost[q] = 0u;
         }
     }
     __syncthreads();
@@ -1216,7 +1250,23 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
         fe26_mul(rhs, t, X);
         fe26_set_small(seven, 7u);
         fe26_add(rhs, rhs, seven);  // w (m 2)
-        if (wave == 2) {
+        if (wave == 2 && kSplit) {
+            if constexpr (kSplit) {  // the head only; the verdict so far, and v's parity for the tail
+                fe26 st[kLive];
+                fe26_sqrt_head<kCut>(st, rhs);
+                if (lane < TPW) {
+#pragma unroll
+                    for (int j = 0; j < kLive; ++j) {
+#pragma unroll
+                        for (int q = 0; q < 10; ++q) L.sq[j][q][lane] = st[j].v[q];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 10; ++q) L.sq[5][q][lane] = rhs.v[q];
+                }
+                L.rflag[lane] = (okr ? 2u : 0u) | ((v & 1u) << 4);
+                COOP_T(6);
+            }
+        } else if (wave == 2) {
             fe26 y, ny;
             fe26_sqrt_cand(y, rhs);
             fe26_sqr(t, y);
@@ -1281,7 +1331,7 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
         coop_post(&L.post[0]);
         COOP_T(7);
     }
-    if (kVer || wave != 2) {
+    if (kVer || kSplit || wave != 2) {
         coop_wait(&L.post[0]);
         coop_wait(&L.post[1]);
         fe e, rinv, u1;
@@ -1300,21 +1350,31 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
                 L.k[1][q][lane] = k2.v[q];
             }
             L.flags[lane] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
+            if constexpr (kSplit) coop_post(&L.spost[0]);  // phase C may start: the table, Zc, k and the flags
         }
         Jac26 G;
         // recover: wave 2 takes the square root, so the comb windows go to waves 0, 3 and 1; verify: wave 2
         // joins (wave 3 also adds wave 0's partial, wave 1 builds the table first)
-        if (tab_bits == kWideBits) {  // 16 windows of the 16-bit comb: 7 / 7 / 2; verify 6 / 4 / 5 / 1
-            const int lo = kVer ? (wave == 0 ? 0 : wave == 3 ? 6 : wave == 2 ? 10 : 15) : (wave == 0 ? 0 : wave == 3 ? 7 : 14);
-            const int hi = kVer ? (wave == 0 ? 6 : wave == 3 ? 10 : wave == 2 ? 15 : 16) : (wave == 0 ? 7 : wave == 3 ? 14 : 16);
+        // with the split root wave 2 joins after the head, and no partial is added here: waves 0 / 3 / 2 / 1
+        // take windows [0, a) / [a, b) / [b, c) / [c, 16) of BCOSGPU_TRIO_SPLIT_WIN = a, b, c
+        const int slo = wave == 0 ? 0 : wave == 3 ? kSw[0] : wave == 2 ? kSw[1] : kSw[2];
+        const int shi = wave == 0 ? kSw[0] : wave == 3 ? kSw[1] : wave == 2 ? kSw[2] : 16;
+        if (kSplit && slo == shi) {
+            CurveK1x::set_inf(G);
+        } else if (tab_bits == kWideBits) {  // 16 windows of the 16-bit comb: 7 / 7 / 2; verify 6 / 4 / 5 / 1
+            const int lo = kSplit ? slo : kVer ? (wave == 0 ? 0 : wave == 3 ? 6 : wave == 2 ? 10 : 15) : (wave == 0 ? 0 : wave == 3 ? 7 : 14);
+            const int hi = kSplit ? shi : kVer ? (wave == 0 ? 6 : wave == 3 ? 10 : wave == 2 ? 15 : 16) : (wave == 0 ? 7 : wave == 3 ? 14 : 16);
             comb_range26w<kWideBits>(G, u1, tab, lo, hi);
         } else {  // 32 windows of the 8-bit comb: 12 / 12 / 8; verify 11 / 8 / 11 / 2
-            const int lo = kVer ? (wave == 0 ? 0 : wave == 3 ? 11 : wave == 2 ? 19 : 30) : (wave == 0 ? 0 : wave == 3 ? 12 : 24);
-            const int hi = kVer ? (wave == 0 ? 11 : wave == 3 ? 19 : wave == 2 ? 30 : 32) : (wave == 0 ? 12 : wave == 3 ? 24 : 32);
+            const int lo = kSplit ? 2 * slo : kVer ? (wave == 0 ? 0 : wave == 3 ? 11 : wave == 2 ? 19 : 30) : (wave == 0 ? 0 : wave == 3 ? 12 : 24);
+            const int hi = kSplit ? 2 * shi : kVer ? (wave == 0 ? 11 : wave == 3 ? 19 : wave == 2 ? 30 : 32) : (wave == 0 ? 12 : wave == 3 ? 24 : 32);
             comb_range26w<8>(G, u1, tab, lo, hi);
         }
         // G0 + G3 on wave 3 while phase A waits for wave 1's last window (one addition off phase D)
-        if (wave == 0) {
+        if constexpr (kSplit) {
+            coop26_store_jac(L.pt[wave == 0 ? 3 : wave == 3 ? 4 : wave == 2 ? 0 : 2], G, lane);
+            coop_post(&L.spost[1 + wave]);
+        } else if (wave == 0) {
             coop26_store_jac(L.pt[2], G, lane);
             coop_post(&L.post[2]);
         } else if (wave == 3) {
@@ -1330,13 +1390,17 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
         }
     }
     COOP_T(1);
-    __syncthreads();
+    // (the split root: each wave enters phase C once wave 1 has posted the table and the scalars; what the
+    // other waves leave in LDS is read in phase D only, behind their own flags or a barrier)
+    if constexpr (kSplit) coop_wait(&L.spost[0]);
+    else __syncthreads();
     // ---------------------------------------------------------------- phase C: two cooperative GLV chains
     if constexpr (TRIO) {
         const TrioLane T(lane);
         const int pos = lane & 15, trio_idx = pos / 3;
         const int chain = wave & 1, tl = (wave >> 1) * 20 + (lane >> 4) * 5 + (trio_idx < 5 ? trio_idx : 4);
-        const uint32_t tflags = L.flags[tl] | L.rflag[tl];
+        // (the split root: wave 2's rflag is read in phase D, behind a barrier)
+        const uint32_t tflags = kSplit ? L.flags[tl] : L.flags[tl] | L.rflag[tl];
         TrioPt acc;
         {
             fe k;
@@ -1363,16 +1427,158 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
         // partials; all three additions are trio_add (6 product levels instead of 16 products on one
         // lane).  Then the inversion and the affine map on lane 2 of each trio, the address Keccak on
         // lane PAIRS (KeccakPair) of the chain-0 waves, and the outputs from lane 2.  The buffers reuse
-        // the table's LDS once every wave is past phase C.
-        uint32_t* const xbuf = &L.tab[0][0][0] + (wave >> 1) * kTrioWords * 64;
-        uint32_t* const gbuf = &L.tab[0][0][0] + (2 + (wave >> 1)) * kTrioWords * 64;
+        // the table's LDS once every wave is past phase C (with the split root, whose chain-1 waves run
+        // ahead, they are Trio26Lds::xg instead, and its own schedule follows below).
+        uint32_t* const xbuf = kSplit ? &L.xg[wave >> 1][0][0] : &L.tab[0][0][0] + (wave >> 1) * kTrioWords * 64;
+        uint32_t* const gbuf =
+            kSplit ? &L.xg[2 + (wave >> 1)][0][0] : &L.tab[0][0][0] + (2 + (wave >> 1)) * kTrioWords * 64;
         uint32_t* const mbuf = &L.tabphx[0][0][0];  // [40][16] pubkey messages, then [40][8] digests
         const uint64_t ti = static_cast<uint64_t>(blockIdx.x) * TPW + tl;
         const bool real = T.r2 && trio_idx < 5, tactive = ti < n;
         fe26 zcy;
         fe ax, ay;
         bool ok2 = false;
-        __syncthreads();  // no wave reads the table any more
+        if constexpr (!kSplit) __syncthreads();  // no wave reads the table any more
+        if constexpr (kSplit) {
+            // The split root's phase D.  The chains' sum S lies on E_w; with l = Zc y and K = l^2 = Zc^2 w it is
+            // the point (X K, Y K l, Z K) of E (trio_scale_xz, trio_scale_y), whose X and Z hold no y.  So the Z
+            // of the last addition T + S_E (T the G part) needs no y: chain 0 computes it alone (trio_add_z)
+            // and starts Z^-1, while chain 1 finishes the root, runs the complete addition and hands over
+            // X3, Y3.  Chain 1's waves leave phase A, and so phase C, before chain 0's: they sum the comb
+            // partials in that lead, behind flags instead of barriers.
+            constexpr bool kPairInv = BCOSGPU_TRIO_INV_SPLIT != 0 && kCut == 1;
+            const auto load_zc_w = [&](fe26& zc, fe26& w) {
+                lds_load_fe26(zc, L.zc, tl);
+#pragma unroll
+                for (int q = 0; q < 10; ++q) w.v[q] = L.sq[5][q][tl];
+                F26_SETM(w, 2);
+            };
+            TrioPt SE;
+            fe26 zi2, zi3;  // chain 0: Z^-2, Z^-3
+            fe26_zero(zi2);
+            fe26_zero(zi3);
+            if (chain == 1) {  // its chain's point to the partner; T = the sum of phase A's comb partials
+                trio_store(xbuf, acc, lane);
+                coop_post(&L.spost[5 + (wave >> 1)]);
+                coop_wait(&L.spost[1 + 0]);
+                coop_wait(&L.spost[1 + 3]);
+                if constexpr (kSw[1] < kSw[2]) coop_wait(&L.spost[1 + 2]);
+                if constexpr (kSw[2] < 16) coop_wait(&L.spost[1 + 1]);
+                Jac26 Ga, Gb;
+                TrioPt A, B;
+                coop26_load_jac(Ga, L.pt[3], tl);
+                coop26_load_jac(Gb, L.pt[4], tl);
+                trio_from_jac(A, Ga, T);
+                trio_from_jac(B, Gb, T);
+                trio_add(A, A, B, T);
+                if constexpr (kSw[1] < kSw[2]) {
+                    coop26_load_jac(Gb, L.pt[0], tl);
+                    trio_from_jac(B, Gb, T);
+                    trio_add(A, A, B, T);
+                }
+                if constexpr (kSw[2] < 16) {
+                    coop26_load_jac(Gb, L.pt[2], tl);
+                    trio_from_jac(B, Gb, T);
+                    trio_add(A, A, B, T);
+                }
+                trio_store(gbuf, A, lane);
+            } else {  // S = k1 R' + k2 phi(R') for the partner, and its X K, Z K here
+                TrioPt P1;
+                coop_wait(&L.spost[5 + (wave >> 1)]);
+                trio_load(P1, xbuf, lane);
+                trio_add(acc, acc, P1, T);
+                trio_store(xbuf, acc, lane);
+                fe26 zc, w, K;
+                coop_wait(&L.spost[1 + 2]);  // w is wave 2's (stored before its comb partial)
+                load_zc_w(zc, w);
+                fe26_sqr(K, zc);
+                fe26_mul(K, K, w);
+                trio_scale_xz(SE, acc, K, T);
+            }
+            __syncthreads();  // every wave is past phase C and phase A; S and T are in LDS
+            const uint32_t rfl = L.rflag[tl];
+            if (chain == 0) {
+                TrioPt G;
+                trio_load(G, gbuf, lane);
+                fe26 Z3;
+                trio_add_z(Z3, G, SE, T);
+                COOP_T(4);
+                fe z, zi;
+                fe26_to_fe(z, Z3);
+                if constexpr (kPairInv) {
+                    FieldK1::normalize(z);
+                    int32_t* const pq = reinterpret_cast<int32_t*>(&L.pt[0][0][0]);
+                    int32_t* const ring = pq + (wave >> 1) * (kInvRing * 4 * 64);
+                    int32_t* const dq = pq + 2 * kInvRing * 4 * 64 + (wave >> 1) * 9 * 64;
+                    const int32_t fs = modinv_pair_fg(z, kMod30K1P, ring, L.invq[wave >> 1], lane);
+                    modinv_pair_finish(zi, fs, kMod30K1P, dq, L.invq[wave >> 1], lane);
+                } else {
+                    FieldInv<FieldK1>::inv_pipe(zi, z);
+                }
+                COOP_T(5);
+                fe26 zi26;
+                fe26_from_fe(zi26, zi);
+                fe26_sqr(zi2, zi26);
+                fe26_mul(zi3, zi2, zi26);
+            } else {
+                TrioPt S, G;
+                trio_load(S, xbuf, lane);
+                trio_load(G, gbuf, lane);
+                fe26 y, ny, t, zc, w, K, l;
+                load_zc_w(zc, w);
+                fe26_sqr(K, zc);
+                fe26_mul(K, K, w);
+                trio_scale_xz(SE, S, K, T);  // (before the tail: less work between y and the hand-over)
+                {
+                    fe26 st[kLive];
+#pragma unroll
+                    for (int j = 0; j < kLive; ++j) {
+#pragma unroll
+                        for (int q = 0; q < 10; ++q) st[j].v[q] = L.sq[j][q][tl];
+                        F26_SETM(st[j], 1);
+                    }
+                    fe26_sqrt_tail<kCut>(y, st);
+                }
+                fe26_sqr(t, y);
+                fe26_sub<3>(t, t, w);
+                const bool on = fe26_is_zero(t);  // y^2 = w: r is the x of a curve point
+                fe26_normalize(y);
+                fe26_neg<2>(ny, y);
+                fe26_normalize(ny);
+                fe26_cmov(y, ny, (y.v[0] & 1u) != ((rfl >> 4) & 1u));
+                COOP_T(4);
+                fe26_mul(l, zc, y);
+                trio_scale_y(SE, l, T);
+                trio_add(S, G, SE, T);  // T first: S_E = T doubles T, which holds no y
+                trio_store(xbuf, S, lane);
+                if (real) L.yok[tl] = on ? 1u : 0u;
+                COOP_T(5);
+                if constexpr (kPairInv) {
+                    const int32_t* const pq = reinterpret_cast<const int32_t*>(&L.pt[0][0][0]);
+                    modinv_pair_de(kMod30K1P, pq + (wave >> 1) * (kInvRing * 4 * 64),
+                                   reinterpret_cast<int32_t*>(&L.pt[0][0][0]) + 2 * kInvRing * 4 * 64 + (wave >> 1) * 9 * 64,
+                                   L.invq[wave >> 1], lane);
+                }
+            }
+            __syncthreads();  // X3, Y3 and the verdicts are in LDS
+            if (chain == 0) {
+                TrioPt O;
+                trio_load(O, xbuf, lane);
+                ok2 = (tflags & 1u) != 0u && (rfl & 2u) != 0u && L.yok[tl] != 0u && !O.inf;
+                fe26 X, Y;  // lane 2 holds X3 (Xs), Y3 (S1)
+                fe26_mul(X, O.Xs, zi2);
+                fe26_mul(Y, O.S1, zi3);
+                fe26_to_fe(ax, X);
+                fe26_to_fe(ay, Y);
+                if (real) {
+                    uint32_t m[16];
+                    fe_to_be_words(m, ax);
+                    fe_to_be_words(m + 8, ay);
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) mbuf[16 * tl + q] = m[q];
+                }
+            }
+        } else {
         if (chain == 1) {
             trio_store(xbuf, acc, lane);
         } else if constexpr (kVer) {
@@ -1472,6 +1678,7 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
                            L.invq[wave >> 1], lane);
         }
 #endif
+        }  // !kSplit
         __syncthreads();
         if (chain == 0 && io.want_addr()) {  // Keccak256(x || y) on lane pairs: tx j = lane / 2 of the wave
             const KeccakPair kp;

@@ -7,6 +7,14 @@
 #include <cstdio>
 #include <vector>
 
+namespace bcosgpu {
+// ecc_coop.hip's launcher names the row kernel's (ecc_row.hip), which this probe neither builds nor runs
+template <class IO>
+int launch_recover_row(const IO&, uint64_t, hipStream_t) {
+    return BCOSGPU_E_ARG;
+}
+}  // namespace bcosgpu
+
 int main(int argc, char** argv) {
     using namespace bcosgpu;
     const bool f26 = argc > 1 && argv[1][0] == '2';  // "26": tx_verify_coop26_kernel
@@ -61,6 +69,11 @@ int main(int argc, char** argv) {
                (unsigned long long)(dt[w][2] - dt[w][0]), (unsigned long long)(dt[w][3] - dt[w][0]),
                (unsigned long long)(dt[w][4] - dt[w][0]), (unsigned long long)(dt[w][5] - dt[w][0]),
                (unsigned long long)(dt[w][6] - dt[w][0]), (unsigned long long)(dt[w][7] - dt[w][0]));
+    // trio with the split square root: waves 0 / 2 stamp the Z^-1 (start, end), waves 1 / 3 the end of the
+    // root's tail and the end of the last addition
+    printf("], \"phase_d_4_5\": [");
+    for (int w = 0; w < 4; ++w)
+        printf("%s[%llu, %llu]", w ? ", " : "", (unsigned long long)(t[w][4] - t[w][0]), (unsigned long long)(t[w][5] - t[w][0]));
     printf("], \"wave0_phase_d\": [%llu, %llu], \"probes\": \"end of phase A work, end of phase C loop, end of kernel; wave 0: before / after the affine inversion\"}\n",
            (unsigned long long)(t[0][4] - t[0][0]), (unsigned long long)(t[0][5] - t[0][0]));
     return 0;
