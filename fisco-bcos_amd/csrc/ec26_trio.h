@@ -264,7 +264,7 @@ F26_HD void trio_dbl(TrioPt& P, const TrioLane& T) {
 // R <- P + Q, Q affine (x, y <= 2) and never infinity; P: X, Y <= 10, Z <= 16 -> (9, 6, 2).  The
 // exceptional cases are those of CurveK1x::madd: P = Q doubles (computed on lane 2, which holds all of
 // P), P = -Q gives infinity, P = infinity gives Q.  EXC = false drops the P = +-Q tests for callers
-// that exclude those cases (trio_add_digit in ecc_coop.hip states why a GLV chain does).
+// that exclude those cases (trio_add_digit_zz in ecc_coop.hip states why a GLV chain does).
 template <bool EXC = true>
 F26_HD void trio_madd(TrioPt& R, const TrioPt& P, const Aff26& Q, const TrioLane& T) {
     using namespace trio;
@@ -384,7 +384,7 @@ F26_HD void trio_dbl_zz(TrioPt& P, fe26& ZZ, const TrioLane& T) {
 
 // R <- P + Q, Q affine, given ZZ = Z1^2 on lane 0 (trio_dbl_zz): CurveK1x::madd in 4 product levels
 // instead of 5 (the Z1^2 level is gone), without the P = +-Q tests (the GLV chain's additions, see
-// trio_add_digit in ecc_coop.hip); P = infinity gives Q.  X, Y <= 10, Z <= 16, ZZ <= 4; Q <= 2
+// trio_add_digit_zz in ecc_coop.hip); P = infinity gives Q.  X, Y <= 10, Z <= 16, ZZ <= 4; Q <= 2
 // -> (9, 6, 2).
 //   L1  U2 = x2 ZZ       | T = y2 Z        | --
 //   L2  HH = H^2         | S2 = T ZZ       | Z H          (H = U2 - X on lane 0)
@@ -433,6 +433,32 @@ F26_HD void trio_madd_zz(TrioPt& R, const TrioPt& P, const fe26& ZZ, const Aff26
     O.inf = false;
     if (P.inf) trio_from_aff(O, Q, T);
     R = O;
+}
+
+// The start of a radix-16 Booth chain over a 128-bit scalar k (top = its highest word): the two top
+// digits, d32 = bit 127 and d31 = (bits 124..127) + (bit 123) - 16 d32, weigh 16 d32 + d31 = t =
+// (top nibble) + (bit 123) in [0, 16] together.  With t = 2a + b, a = t >> 1 <= 8, b = t & 1:
+// acc <- 2 (a R) + b R, the table's a R taken as the accumulator (a = 0: infinity), one doubling and one
+// 4-level addition -- 7 product levels where a 5-level addition onto infinity, four doublings and an
+// addition took 21.  entry(S, d) gives the signed table point S = +-d R, d in [1, 8] (x, y <= 2; for
+// d = 0 any entry).  No P = +-Q case: 2a = +-b only for a = 0, the infinity flag.  -> (10, 10, 2) as a
+// window's end (the doubling's bound; the addition's (9, 6, 2) lies inside it), infinity for t = 0; the
+// chain goes on at digit 30.
+template <class Entry>
+F26_HD void trio_chain_start(TrioPt& acc, uint32_t top, const Entry& entry, const TrioLane& T) {
+    const uint32_t t = (top >> 28) + ((top >> 27) & 1u);
+    const int a = static_cast<int>(t >> 1), b = static_cast<int>(t & 1u);
+    Aff26 S;
+    TrioPt R;
+    fe26 zz;
+    entry(S, a);
+    trio_from_aff(R, S, T);
+    trio_set_inf(acc);
+    trio_cmov(acc, R, a != 0);
+    trio_dbl_zz(acc, zz, T);
+    entry(S, 1);
+    trio_madd_zz(R, acc, zz, S, T);
+    trio_cmov(acc, R, b != 0);
 }
 
 // R <- P + Q, both Jacobian in trio form (lane 2 holds all of each point at entry); CurveK1x::add's

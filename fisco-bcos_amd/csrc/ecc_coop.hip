@@ -1070,18 +1070,12 @@ __device__ __forceinline__ void trio_from_jac(TrioPt& P, const Jac26& J, const T
     P.inf = J.inf;
 }
 
-// A window of a GLV chain: acc <- acc + d * (table point), d a Booth digit in [-8, 8].  The madd runs
-// without its P = Q / P = -Q tests (trio_madd<false>): acc is K R for the digits K processed so far
-// and the table point is |d| R with |d| <= 8; once K != 0 every window makes |K| >= 16 before its
-// addition, so K = +-d (mod n) would need 16 <= |K| <= 8 -- impossible for |K| < 2^130 < n and R of
-// order n.  (An R that is not on the curve fails its verdict and its chain's value is discarded.)
-// K = 0 is the infinity flag, which the madd handles.
-__device__ __forceinline__ void trio_add_digit(TrioPt& acc, const Trio26Lds& L, int tl, int d, bool neg, bool phi,
-                                               const TrioLane& T) {
+// The signed table point of a GLV chain: S = +-|d| R for a Booth digit d in [-8, 8] (phi: of phi(R)); for
+// d = 0 an entry whose value the caller discards.
+__device__ __forceinline__ void trio_entry(Aff26& S, const Trio26Lds& L, int tl, int d, bool neg, bool phi) {
     const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
     const uint32_t* base = &L.tab[0][0][0] + m * (20 * 64) + tl;
     const uint32_t* bx = phi ? &L.tabphx[0][0][0] + m * (10 * 64) + tl : base;
-    Aff26 S;
 #pragma unroll
     for (int q = 0; q < 10; ++q) {
         S.x.v[q] = bx[q * 64];
@@ -1092,30 +1086,21 @@ __device__ __forceinline__ void trio_add_digit(TrioPt& acc, const Trio26Lds& L, 
     fe26 ny;
     fe26_neg<2>(ny, S.y);
     fe26_cmov(S.y, ny, (d < 0) != neg);
-    TrioPt R;
-    trio_madd<false>(R, acc, S, T);
-    trio_cmov(acc, R, d != 0);
 }
 
-// the same window step after trio_dbl_zz: the addition in 4 product levels (trio_madd_zz).  (Reading
-// the table entry before the window's doublings, to take the LDS latency off the first level, measured
-// no gain: 893k cycles either way.)
+// A window of a GLV chain, after trio_dbl_zz: acc <- acc + d * (table point), d a Booth digit in [-8, 8],
+// in 4 product levels (trio_madd_zz).  The addition runs without P = Q / P = -Q tests: acc is K R for the
+// digits K processed so far and the table point is |d| R with |d| <= 8; once K != 0 every window makes
+// |K| >= 16 before its addition, so K = +-d (mod n) would need 16 <= |K| <= 8 -- impossible for
+// |K| < 2^130 < n and R of order n.  (An R that is not on the curve fails its verdict and its chain's
+// value is discarded.)  K = 0 is the infinity flag, which the addition handles.  The chain's start
+// (trio_chain_start, ec26_trio.h) adds b <= 1 to K = 2a, a <= 8: 2a = +-b only for a = 0, the flag again.
+// (Reading the table entry before the window's doublings, to take the LDS latency off the first level,
+// measured no gain: 893k cycles either way.)
 __device__ __forceinline__ void trio_add_digit_zz(TrioPt& acc, const Trio26Lds& L, int tl, int d, bool neg, bool phi,
                                                   const fe26& ZZ, const TrioLane& T) {
-    const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
-    const uint32_t* base = &L.tab[0][0][0] + m * (20 * 64) + tl;
-    const uint32_t* bx = phi ? &L.tabphx[0][0][0] + m * (10 * 64) + tl : base;
     Aff26 S;
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-        S.x.v[q] = bx[q * 64];
-        S.y.v[q] = base[(10 + q) * 64];
-    }
-    F26_SETM(S.x, 1);
-    F26_SETM(S.y, 1);
-    fe26 ny;
-    fe26_neg<2>(ny, S.y);
-    fe26_cmov(S.y, ny, (d < 0) != neg);
+    trio_entry(S, L, tl, d, neg, phi);
     TrioPt R;
     trio_madd_zz(R, acc, ZZ, S, T);
     trio_cmov(acc, R, d != 0);
@@ -1409,10 +1394,11 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
             for (int q = 0; q < 4; ++q) k.v[q] = L.k[chain][q][tl];
             const bool neg = chain == 0 ? (tflags & 4u) != 0 : (tflags & 8u) != 0;
             const bool phi = chain == 1;
-            trio_set_inf(acc);
-            trio_add_digit(acc, L, tl, static_cast<int>(k.v[3] >> 31), neg, phi, T);  // digit 32 = bit 127
+            // digits 32 and 31 together (16 d32 + d31 = 2a + b): a R from the table, one doubling, b R
+            trio_chain_start(acc, k.v[3], [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
+            shl4_128(k);  // booth_digit128 goes on at digit 30
 #pragma unroll 1
-            for (int w = 31; w >= 0; --w) {
+            for (int w = 30; w >= 0; --w) {
                 fe26 zz;
 #pragma unroll kTrioDblUnroll
                 for (int q = 0; q < 3; ++q) trio_dbl(acc, T);
