@@ -461,6 +461,177 @@ F26_HD void trio_chain_start(TrioPt& acc, uint32_t top, const Entry& entry, cons
     trio_cmov(acc, R, b != 0);
 }
 
+// ------------------------------------------------------------------ the lean window
+// A window of a radix-16 chain (four doublings and the addition of a signed table point) with fewer
+// routing and small-constant instructions between the same 16 product levels.  What changes against
+// trio_dbl x 3, trio_dbl_zz, trio_madd_zz:
+//   * the state is TrioAcc: S1 = (X | Y | Y) and Zs = Z on lane 2.  X is not kept on lane 2 between
+//     operations: the lane that multiplies by X fetches it from lane 0's S1 inside the select that builds
+//     its operand (one v_cndmask_b32_dpp per limb where a DPP move and a select stood);
+//   * a doubling returns -2P = (X3, -Y3, Z3) (Z3 up to a power of two that the window settles once): -Y3 = E (X3 - D) + 8C is an addition (one v_lshl_add_u32 per
+//     limb) where Y3 = E (D - X3) - 8C adds a multiple of p and subtracts.  The next doubling squares Y and
+//     takes Z3 = 2 Y Z on the negated point, so four doublings give +16P; Z3^2 = 4 B Z^2 does not see the sign;
+//   * the second level's operand is (3A | 2B | 2B), one v_lshl_add_u32 with a per-lane shift and no select:
+//     the level then returns (F | 4C | 2XB), from which X3 = F - 4 (2XB), X3 - D = X3 - 2 (2XB) and
+//     8C = 2 (4C) follow without the temporaries D and 2D, all under one added multiple of p;
+//   * the addition is the unscaled one, Z3 = Z H, X3 = rr^2 - H^3 - 2 X H^2, Y3 = rr (X H^2 - X3) - Y H^3
+//     (another representative of the same point: no 4 HH, 4 rr^2, 2 (...)), with rr and T = y2 Z on lane 2,
+//     which holds Y and Z, and Z H on the last level's idle lane;
+//   * an infinite accumulator sits behind a wave-uniform branch, and the digit-0 case is one select per
+//     limb of S1 and Zs.
+struct TrioAcc {
+    fe26 S1, Zs;
+    bool inf;
+};
+F26_HD void trio_acc_from(TrioAcc& A, const TrioPt& P) {
+    fe26_copy(A.S1, P.S1);
+    fe26_copy(A.Zs, P.Zs);
+    A.inf = P.inf;
+}
+F26_HD void trio_acc_to(TrioPt& P, const TrioAcc& A, const TrioLane&) {
+    fe26_copy(P.S1, A.S1);
+    trio::fdpp<trio::kL2>(P.Xs, A.S1);                   // lane 2 <- X of lane 0
+    fe26_copy(P.Zs, A.Zs);
+    P.inf = A.inf;
+}
+
+// The window's doubling number STEP = 0..3: P <- -2P, and the last one (STEP 3) also gives ZZ = Z3^2 on lane 0
+// (m 1) as trio_dbl_zz does.  X, Y, Z <= 16 -> (9, 3, .).
+//   L1  A = X^2          | B = Y^2            | B   (STEP 3: Z^2, and 2B comes from lane 1)
+//   L2  F = (3A)^2       | 4C = (2B)^2        | x = X 2B             (X from lane 0)
+//   L3  -- (3: B Z^2)    | E (X3 - D)         | Y Z                  (E = 3A from lane 0)
+//   lane 1: G = F + 8p, X3 = G - 4x, X3 - D = X3 - 2x (limb by limb 8 p_i >= 6 x_i: x is a product, m 1),
+//   -Y3 = E (X3 - D) + 2 (4C).
+// Z3 = 2 Y Z is not doubled at every step: between the steps Zs holds a power of two times Z, and one shift per
+// window stands where four doublings of Z and the scaling of Z^2 stood:
+//   step 0  Zs = Z       -> Y Z = Z3 / 2                                (m 1)
+//   step 1  Zs = Z / 2   -> Y Z / 2 = Z3 / 4                            (m 1)
+//   step 2  Zs = Z / 4   -> 16 (Y Z / 4) = 2 Z3                         (m 16)
+//   step 3  Zs = 2 Z     -> Y (2 Z) = Z3 (m 1), and ZZ = B (2 Z)^2 = 4 B Z^2 = Z3^2.
+// Only X and Y of steps 0..2 are a point's coordinates with that Zs; trio_window runs the four in order.
+template <int STEP>
+F26_HD void trio_dbln(TrioAcc& P, fe26& ZZ, const TrioLane& T) {
+    using namespace trio;
+    static_assert(STEP >= 0 && STEP <= 3, "a window has four doublings");
+    constexpr bool WZZ = STEP == 3;
+    fe26 S0, o1, T2, S2, o2, F, x, X3, Wn, P3, Q3, o3, Y3, t;
+    if constexpr (WZZ) {
+        sel(S0, T.r2, P.Zs, P.S1);                       // (X | Y | 2 Z)
+        sqr(o1, S0);                                     // (A | B | 4 Z^2)              m 1
+    } else {
+        sqr(o1, P.S1);                                   // (A | B | B)                  m 1
+    }
+    const uint32_t sh = T.r0 ? 1u : 0u;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) T2.v[i] = (o1.v[i] << sh) + o1.v[i];  // one v_lshl_add_u32
+    F26_SETM(T2, T.r0 ? 3 : 2);                          // (3A | 2B | 2B)               m <= 3
+    if constexpr (WZZ) csel<kL1>(T2, !T.r2, T.n2, T2, T2);  // lane 2: 2B of lane 1
+    csel<kL2>(S2, !T.r2, T.n2, T2, P.S1);                // (3A | 2B | X of lane 0)      m <= 16
+    mul(o2, S2, T2);                                     // (F | 4C | x)
+    fdpp<kL1>(F, o2);                                    // lane 1: F                    m 1
+    fdpp<kR1>(x, o2);                                    // lane 1: x = 2 X B            m 1
+    F26_REQ(F.m <= 1 && x.m <= 1);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t g = F.v[i] + 8u * f26::plimb(i);
+        X3.v[i] = g - (x.v[i] << 2);                     // X3 = F - 2D                  m 9
+        Wn.v[i] = X3.v[i] - (x.v[i] << 1);               // X3 - D                       m 9
+    }
+    F26_SETM(X3, 9);
+    F26_SETM(Wn, 9);
+    F26_CHK(X3);
+    F26_CHK(Wn);
+    csel<kL1>(P3, T.r2, T.m2, P.S1, T2);                 // lane 1: E = 3A (lane 0), lane 2: Y
+    sel(Q3, T.r2, P.Zs, Wn);                             // lane 1: X3 - D, lane 2: Zs
+    if constexpr (WZZ) {
+        csel<kR1>(P3, !T.r0, T.n0, P3, o1);              // lane 0: B (lane 1)
+        csel<kR2>(Q3, !T.r0, T.n0, Q3, o1);              // lane 0: 4 Z^2 (lane 2)
+    }
+    mul(o3, P3, Q3);                                     // (- or Z3^2 | E (X3 - D) | Y Zs)
+    if constexpr (WZZ) fe26_copy(ZZ, o3);                // lane 0: Z3^2                 m 1
+#pragma unroll
+    for (int i = 0; i < 10; ++i) Y3.v[i] = (o2.v[i] << 1) + o3.v[i];  // lane 1: -Y3 = o3 + 8C
+    F26_SETM(Y3, 3);
+    F26_CHK(Y3);
+    if constexpr (STEP == 2) fe26_mul_int<16>(P.Zs, o3); // lane 2: 2 Z3                 m 16
+    else fe26_copy(P.Zs, o3);                            // lane 2: Z3 / 2, Z3 / 4, Z3   m 1
+    csel<kL1>(t, T.r1, T.m1, Y3, Y3);                    // lanes 1, 2: -Y3 of lane 1
+    csel<kR1>(P.S1, !T.r0, T.n0, t, X3);                 // lane 0: X3 of lane 1
+}
+
+// P <- keep ? P : P + Q, Q affine (x, y <= 2) and never infinity, given ZZ = Z^2 on lane 0 (trio_dbln<3>);
+// P = infinity gives Q.  The unscaled mixed addition in the same 4 product levels as trio_madd_zz:
+//   L1  U2 = x2 ZZ       | --                 | T = y2 Z
+//   L2  HH = H^2         | --                 | S2 = T ZZ            (H = U2 - X on lane 0)
+//   L3  J = H HH         | V = X HH           | rr^2                 (rr = S2 - Y on lane 2)
+//   L4  rr (V - X3)      | Y J                | Z3 = Z H             (X3 = rr^2 - J - 2V on lane 0)
+//   lane 1: Y3 = rr (V - X3) - Y J.
+// No P = +-Q test: the argument of trio_add_digit_zz (ecc_coop.hip) bounds the multiples |K| >= 16 of the
+// accumulator and |d| <= 8 of the table point, and is the same for -P as for P; here the accumulator is
+// +16 K R in any case, the window's four doublings having restored the sign.
+// X, Y <= 10, Z <= 16, ZZ <= 4; Q <= 2 -> (5, 3, 1), or P unchanged.
+F26_HD void trio_maddq_zz(TrioAcc& P, const fe26& ZZ, const Aff26& Q, bool keep, const TrioLane& T) {
+    using namespace trio;
+    fe26 A1, B1, o1, h, A2, B2, o2, rr, t, u, A3, B3, o3, R2, V, s, X3, W, A4, B4, o4, Y3, Z3;
+    sel(A1, T.r0, Q.x, Q.y);                             // (x2 | - | y2)
+    sel(B1, T.r0, ZZ, P.Zs);                             // (ZZ | - | Z)
+    mul(o1, A1, B1);                                     // (U2 | - | T)
+    fe26_sub<11>(h, o1, P.S1);                           // lane 0: H = U2 - X           m 12
+    sel(A2, T.r0, h, o1);                                // (H | - | T)
+    csel<kL2>(B2, !T.r2, T.n2, h, ZZ);                   // (H | - | ZZ of lane 0)
+    mul(o2, A2, B2);                                     // (HH | - | S2)
+    fe26_sub<11>(rr, o2, P.S1);                          // lane 2: rr = S2 - Y          m 12
+    sel(t, T.r0, h, rr);
+    csel<kL1>(A3, !T.r1, T.n1, t, P.S1);                 // (H | X of lane 0 | rr)
+    sel(u, T.r0, o2, rr);
+    csel<kL1>(B3, !T.r1, T.n1, u, o2);                   // (HH | HH of lane 0 | rr)
+    mul(o3, A3, B3);                                     // (J | V | rr^2)
+    // lane 0: X3 = rr^2 - (J + 2V) and V - X3
+    fdpp<kR2>(R2, o3);                                   // rr^2 of lane 2               m 1
+    fdpp<kR1>(V, o3);                                    // V of lane 1                  m 1
+    F26_REQ(V.m <= 1);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) s.v[i] = (V.v[i] << 1) + o3.v[i];  // J + 2V           m 3
+    F26_SETM(s, 3);
+    fe26_sub<4>(X3, R2, s);                              // X3                           m 5
+    fe26_sub<6>(W, V, X3);                               // V - X3                       m 7
+    csel<kL1>(t, !T.r1, T.n1, W, o3);                    // lane 1: J of lane 0
+    csel<kL2>(A4, !T.r2, T.n2, t, h);                    // (V - X3 | J | H of lane 0)
+    sel(u, T.r2, P.Zs, P.S1);
+    csel<kR2>(B4, !T.r0, T.n0, u, rr);                   // (rr of lane 2 | Y | Z)
+    mul(o4, A4, B4);                                     // (rr (V - X3) | Y J | Z H)
+    fdpp<kL1>(t, o4);
+    fe26_sub<2>(Y3, t, o4);                              // lane 1: Y3                   m 3
+    sel(s, T.r0, X3, Y3);
+    csel<kL1>(s, !T.r2, T.n2, s, Y3);                    // (X3 | Y3 | Y3 of lane 1)
+    fe26_copy(Z3, o4);                                   // lane 2: Z3                   m 1
+    if (any(P.inf)) {                                    // infinity + Q = Q (no real signature past its
+        fe26 one;                                        // first non-zero digit)
+        sel(t, T.r0, Q.x, Q.y);
+        fe26_one(one);
+        fe26_cmov(s, t, P.inf);
+        fe26_cmov(Z3, one, P.inf);
+    }
+    sel(P.S1, keep, P.S1, s);
+    sel(P.Zs, keep, P.Zs, Z3);
+    P.inf = keep && P.inf;
+}
+
+// One window of a radix-16 Booth chain: acc <- 16 acc + d S, d in [-8, 8]; entry(S, d) gives the signed
+// table point as for trio_chain_start.  X, Y, Z <= 16 -> (9, 3, 1) (d = 0) or (5, 3, 1), inside the
+// entry contract of the next window, of trio_add and of trio_scale_xz.
+template <class Entry>
+F26_HD void trio_window(TrioAcc& acc, int d, const Entry& entry, const TrioLane& T) {
+    fe26 zz;
+    trio_dbln<0>(acc, zz, T);
+    trio_dbln<1>(acc, zz, T);
+    trio_dbln<2>(acc, zz, T);
+    trio_dbln<3>(acc, zz, T);                            // + Z^2 for the addition
+    Aff26 S;
+    entry(S, d);
+    trio_maddq_zz(acc, zz, S, d == 0, T);
+}
+
 // R <- P + Q, both Jacobian in trio form (lane 2 holds all of each point at entry); CurveK1x::add's
 // formulas, magnitudes and exceptional cases (P = Q doubles on lane 2, P = -Q gives infinity, an
 // infinite operand gives the other), 16 products in 6 levels:

@@ -1116,6 +1116,12 @@ enum { kRecover = 0, kVerify = 1 };
 #ifndef kTrioDblUnroll
 #define kTrioDblUnroll 3  // phase C doublings per window unrolled (rolled, 1: 0.385 vs 0.383 ms)
 #endif
+// Phase C's windows: 1 the lean window (trio_window, ec26_trio.h: the same 16 product levels with fewer routing
+// and small-constant instructions between them), 0 the earlier one (trio_dbl x 3, trio_dbl_zz,
+// trio_add_digit_zz; A/B).  The chain start is the same for both.
+#ifndef BCOSGPU_TRIO_WINDOW
+#define BCOSGPU_TRIO_WINDOW 1
+#endif
 #ifndef BCOSGPU_TRIO_INV_SPLIT
 #define BCOSGPU_TRIO_INV_SPLIT 1  // phase-D Z^-1 over wave pairs (0 = the one-wave pipelined loop, A/B)
 #endif
@@ -1397,6 +1403,14 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
             // digits 32 and 31 together (16 d32 + d31 = 2a + b): a R from the table, one doubling, b R
             trio_chain_start(acc, k.v[3], [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
             shl4_128(k);  // booth_digit128 goes on at digit 30
+#if BCOSGPU_TRIO_WINDOW
+            TrioAcc la;
+            trio_acc_from(la, acc);
+#pragma unroll 1
+            for (int w = 30; w >= 0; --w)
+                trio_window(la, booth_digit128(k), [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
+            trio_acc_to(acc, la, T);
+#else
 #pragma unroll 1
             for (int w = 30; w >= 0; --w) {
                 fe26 zz;
@@ -1405,6 +1419,7 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
                 trio_dbl_zz(acc, zz, T);  // + Z^2 for the addition
                 trio_add_digit_zz(acc, L, tl, booth_digit128(k), neg, phi, zz, T);
             }
+#endif
         }
         COOP_T(2);
         // ------------------------------------------------------------ phase D on the trios

@@ -1,6 +1,8 @@
 // triobench.hip -- the lane-trio point operations (csrc/ec26_trio.h) against the one-lane CurveK1x
 // ones: the same windows (4 doublings + 1 mixed addition) from the same random inputs, results
-// compared on the host, and s_memtime cycles per window of a lone wave per SIMD for both.
+// compared on the host, and s_memtime cycles per window of a lone wave per SIMD for both.  With ops = 4 a
+// third mode runs the lean window (trio_window), whose point is another Jacobian representative of the same
+// point and is compared projectively.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -25,7 +27,8 @@ __device__ __forceinline__ void load_fe26(fe26& a, const uint32_t* p) {
     fe26_from_words(a, w);
 }
 
-// mode 0: trio, mode 1: one lane per point (every lane of a trio computes its point)
+// mode 0: trio, mode 1: one lane per point (every lane of a trio computes its point), mode 2: the lean
+// window (ops = 4 only; the digit is a kernel argument, so its keep-select stays in the loop)
 __global__ __launch_bounds__(256, 1) void trio_bench(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
                                                      unsigned long long* __restrict__ cyc, int iters, int mode, int ops) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -69,6 +72,21 @@ __global__ __launch_bounds__(256, 1) void trio_bench(const uint32_t* __restrict_
             }
         }
         t1 = clock64();
+        trio_to_jac(J, P, T);
+    } else if (mode == 2) {
+        TrioPt P;
+        trio::sel(P.S1, T.r0, J.X, J.Y);
+        fe26_copy(P.Xs, J.X);
+        fe26_copy(P.Zs, J.Z);
+        P.inf = false;
+        TrioAcc A;
+        trio_acc_from(A, P);
+        const int d = ops >> 2;  // 1
+        t0 = clock64();
+#pragma unroll 1
+        for (int it = 0; it < iters; ++it) trio_window(A, d, [&](Aff26& S, int) { S = Q; }, T);
+        t1 = clock64();
+        trio_acc_to(P, A, T);
         trio_to_jac(J, P, T);
     } else {
         t0 = clock64();
@@ -127,13 +145,15 @@ int main(int argc, char** argv) {
     hipMalloc(&dcyc, blocks * 4 * 8);
     hipMemcpy(din, in.data(), in.size() * 4, hipMemcpyHostToDevice);
     std::vector<unsigned long long> c(blocks * 4);
-    double cw[2] = {0, 0};
-    for (int mode = 0; mode < 2; ++mode) {
+    std::vector<uint32_t> o2(npts * 32);
+    double cw[3] = {0, 0, 0};
+    const int modes = ops == 4 ? 3 : 2;
+    for (int mode = 0; mode < modes; ++mode) {
         for (int rep = 0; rep < 3; ++rep) {
             hipLaunchKernelGGL(trio_bench, dim3(blocks), dim3(256), 0, 0, din, dout, dcyc, iters, mode, ops);
             hipDeviceSynchronize();
         }
-        hipMemcpy(mode ? o1.data() : o0.data(), dout, o0.size() * 4, hipMemcpyDeviceToHost);
+        hipMemcpy(mode == 0 ? o0.data() : mode == 1 ? o1.data() : o2.data(), dout, o0.size() * 4, hipMemcpyDeviceToHost);
         hipMemcpy(c.data(), dcyc, c.size() * 8, hipMemcpyDeviceToHost);
         unsigned long long s = 0;
         for (auto v : c) s += v;
@@ -174,7 +194,27 @@ int main(int argc, char** argv) {
     int bad = 0;
     for (int i = 0; i < npts; ++i)
         if (memcmp(&o0[i * 32], &o1[i * 32], 25 * 4)) ++bad;
+    int bad_lean = 0;
+    if (modes == 3) {  // X_a Z_b^2 = X_b Z_a^2 and Y_a Z_b^3 = Y_b Z_a^3 against the one-lane point
+        auto ld = [](fe26& a, const uint32_t* q) { fe26_from_words(a, q); };
+        auto same = [](fe26 a, fe26 b) { fe26_normalize(a); fe26_normalize(b); return memcmp(a.v, b.v, 40) == 0; };
+        for (int i = 0; i < npts; ++i) {
+            fe26 Xa, Ya, Za, Xb, Yb, Zb, za2, zb2, za3, zb3, l, r;
+            ld(Xa, &o2[i * 32]); ld(Ya, &o2[i * 32 + 8]); ld(Za, &o2[i * 32 + 16]);
+            ld(Xb, &o1[i * 32]); ld(Yb, &o1[i * 32 + 8]); ld(Zb, &o1[i * 32 + 16]);
+            fe26_sqr(za2, Za); fe26_sqr(zb2, Zb); fe26_mul(za3, za2, Za); fe26_mul(zb3, zb2, Zb);
+            fe26_mul(l, Xa, zb2); fe26_mul(r, Xb, za2);
+            bool ok = same(l, r) && o2[i * 32 + 24] == o1[i * 32 + 24];
+            fe26_mul(l, Ya, zb3); fe26_mul(r, Yb, za3);
+            ok = ok && same(l, r);
+            fe26 zero;
+            fe26_zero(zero);
+            if (!ok || same(Za, zero)) ++bad_lean;
+        }
+    }
     printf("{\"points\": %d, \"mismatch\": %d, \"cycles_per_window_trio\": %.0f, \"cycles_per_window_one_lane\": %.0f, "
-           "\"ops\": %d}\n", npts, bad, cw[0], cw[1], ops);
-    return bad ? 1 : 0;
+           "\"ops\": %d", npts, bad, cw[0], cw[1], ops);
+    if (modes == 3) printf(", \"mismatch_lean\": %d, \"cycles_per_window_lean\": %.0f", bad_lean, cw[2]);
+    printf("}\n");
+    return bad || bad_lean ? 1 : 0;
 }
