@@ -22,8 +22,10 @@
 //   sub<K>   : a + K Q - b with Q = 16 p in radix-2^26 digits (each within 2^-12 of 2^26, so K Q >= b
 //              limb by limb when b.m <= K - 1)  -> m_a + K
 // the same contracts as fe26.h's, so ec_row.h's point formulas keep ec26.h's magnitude schedule.
-// The bounds are checked by tools/rowbench.hip on the GPU (every product of every chain, lanes 10..15
-// zero, limbs under the stated bound) and the results against fe26's one-lane products.
+// Checked on the GPU by tests/test_gpu_row_field.py (tools/rowvec.hip: one op per row on operands with every
+// limb at m B for m up to 16, against Python integers: the value mod p, lanes 10..15 zero, limbs under the
+// stated bound, and a row's result independent of the other three rows); tools/rowbench.hip times chains
+// and compares them with fe26's one-lane products.
 #pragma once
 #include <stdint.h>
 
@@ -170,8 +172,8 @@ __device__ __forceinline__ uint32_t mul_int(uint32_t a) { return a * C; }
 // M_1 are < 2^229 and < 2^255) and lane 9's bits from 2^256 (D = 2^256 mod p) fold once more, which
 // leaves a value < 2^257, and two carry rounds bring every limb under B.  Same magnitude contracts as
 // the secp256k1 field; sub<K> adds K Q2 with Q2 = 16 p in digits within 2^-4 of 2^26, so K Q2 >= b limb
-// by limb for b.m <= K - 1 up to K = 15.  Checked on the GPU by tools/rowbench.hip against a host
-// reference, and in Python (every bound above) at magnitude 16.
+// by limb for b.m <= K - 1 up to K = 15.  Checked on the GPU by tests/test_gpu_row_field.py
+// at magnitude 16 (value mod p and every limb <= B, which is where "nothing leaves lane 9" would show).
 // 2^(26 (10 + j)) mod p for j = 0..10, D = 2^256 mod p and Q2 = 16 p (digit 2 raised by 2^26, digit 3
 // lowered by 1, so every digit is within 2^-4 of 2^26), radix-2^26 digits per lane (lanes 10..15: 0)
 __device__ __constant__ static const uint32_t kSm2RowM[11][16] = {

@@ -23,7 +23,10 @@
 //   mul_int<C>     : m * C
 //   normalize_weak : any m <= 63               -> 2
 //   normalize      : any m <= 63               -> canonical
-// The host build with FE26_CHECK (tests/cpp/fp26_test.cpp) asserts them.
+// The host build with FE26_CHECK (tests/cpp/fp26_test.cpp) asserts them.  Op by op, on operands at these
+// bounds, they are checked against Python integers twice: on the device, where mul and sqr are the asm blocks
+// of fe_asm.h (tools/f26vec.hip, tests/test_gpu_f26.py), and on the host with FE26_CHECK over the same case
+// file (tests/test_f26vec_host.py); fe26.h's table likewise.
 #pragma once
 #include "fe26.h"
 
@@ -218,7 +221,8 @@ F26_HD void fp26_mul_int(fp26& r, const fp26& a) {
 }
 
 // one carry pass and one fold of the bits at 2^256 and above (2^256 = 2^224 + 2^96 - 2^64 + 1):
-// limbs 0..8 < 2^26, limb 9 < 2^22 + 2^5 (m = 2), value < 2^256 + 2^240; signed intermediates
+// limbs 0..8 < 2^26, limb 9 < 2^22 + 2^6 (m = 2: the carry out of limb 8 of a magnitude-63 operand is up to
+// 63; tests/f26_vectors.py sees 62), value < 2^256 + 2^240; signed intermediates
 F26_HD void fp26_normalize_weak(fp26& r) {
     using namespace p26;
     P26_CHK(r);

@@ -66,3 +66,30 @@ def test_fieldk1_vs_python():
         want = {"add": a + b, "sub": a - b, "mul": a * b, "sqr": a * a, "norm": a, "shl1": 2 * a,
                 "shl2": 4 * a, "shl3": 8 * a, "mul3": 3 * a}[op] % P
         assert g == want, (op, hex(a), hex(b), hex(g), hex(want))
+
+
+def test_fetest_rejects_unknown_ops():
+    """A typo in a case file is an error (exit status 2, no output), with or without a field selector: it
+    must not pass as a `norm`.  The tool stops before its first HIP call, so this needs no GPU; it does need
+    lib/fetest, which `make -C fisco-bcos_amd` (build()) compiles with hipcc and links against the HIP runtime,
+    so without a prior build it fails on the assert below, not on what it tests."""
+    assert os.path.exists(EXE), "build fisco-bcos_amd/lib/fetest first (make -C fisco-bcos_amd)"
+    for line in ("foo 1 2", "k1:foo 1 2", "p2:norm 1 2", "q7:mul 1 2", "n1:gcd_fast 1 2"):
+        r = subprocess.run([EXE], input=line + "\n", capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and r.stdout == "", (line, r.returncode, r.stdout)
+
+
+@pytest.mark.gpu
+def test_montgomery_fields_and_inversions_vs_python():
+    """FieldP2 (redc_sm2p), FieldN1 and FieldN2 with their mod_add_asm / mod_sub_asm, both Fermat chains of
+    Mont<>::inv, FieldP2::inv, and the safegcd inversions (plain, pipelined, variable-time, and behind
+    mont_inv_safegcd) with each modulus' ModInfo30, through fetest's field selector; cases and checker are
+    tests/mont_vectors.py.  The lane-split inversions (modinv_var_split_*, modinv_pair_*, inv_fg_rows) need
+    their kernels' LDS queues and stay covered end to end."""
+    import mont_vectors as mv
+    assert os.path.exists(EXE), "build fisco-bcos_amd/lib/fetest first (make -C fisco-bcos_amd)"
+    cs = mv.cases()
+    r = subprocess.run([EXE], input=mv.text(cs), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    seen = mv.check_all(cs, r.stdout.split())
+    assert all(seen[k] > 0 for k in ("edge", "tail", "redc_mid", "redc_top", "random")), seen
