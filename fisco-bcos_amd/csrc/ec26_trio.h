@@ -264,7 +264,7 @@ F26_HD void trio_dbl(TrioPt& P, const TrioLane& T) {
 // R <- P + Q, Q affine (x, y <= 2) and never infinity; P: X, Y <= 10, Z <= 16 -> (9, 6, 2).  The
 // exceptional cases are those of CurveK1x::madd: P = Q doubles (computed on lane 2, which holds all of
 // P), P = -Q gives infinity, P = infinity gives Q.  EXC = false drops the P = +-Q tests for callers
-// that exclude those cases (trio_add_digit_zz in ecc_coop.hip states why a GLV chain does).
+// that exclude those cases (trio_glv_chain in ecc_coop.hip states why a GLV chain does).
 template <bool EXC = true>
 F26_HD void trio_madd(TrioPt& R, const TrioPt& P, const Aff26& Q, const TrioLane& T) {
     using namespace trio;
@@ -384,7 +384,7 @@ F26_HD void trio_dbl_zz(TrioPt& P, fe26& ZZ, const TrioLane& T) {
 
 // R <- P + Q, Q affine, given ZZ = Z1^2 on lane 0 (trio_dbl_zz): CurveK1x::madd in 4 product levels
 // instead of 5 (the Z1^2 level is gone), without the P = +-Q tests (the GLV chain's additions, see
-// trio_add_digit_zz in ecc_coop.hip); P = infinity gives Q.  X, Y <= 10, Z <= 16, ZZ <= 4; Q <= 2
+// trio_glv_chain in ecc_coop.hip); P = infinity gives Q.  X, Y <= 10, Z <= 16, ZZ <= 4; Q <= 2
 // -> (9, 6, 2).
 //   L1  U2 = x2 ZZ       | T = y2 Z        | --
 //   L2  HH = H^2         | S2 = T ZZ       | Z H          (H = U2 - X on lane 0)
@@ -566,7 +566,7 @@ F26_HD void trio_dbln(TrioAcc& P, fe26& ZZ, const TrioLane& T) {
 //   L3  J = H HH         | V = X HH           | rr^2                 (rr = S2 - Y on lane 2)
 //   L4  rr (V - X3)      | Y J                | Z3 = Z H             (X3 = rr^2 - J - 2V on lane 0)
 //   lane 1: Y3 = rr (V - X3) - Y J.
-// No P = +-Q test: the argument of trio_add_digit_zz (ecc_coop.hip) bounds the multiples |K| >= 16 of the
+// No P = +-Q test: the argument of trio_glv_chain (ecc_coop.hip) bounds the multiples |K| >= 16 of the
 // accumulator and |d| <= 8 of the table point, and is the same for -P as for P; here the accumulator is
 // +16 K R in any case, the window's four doublings having restored the sign.
 // X, Y <= 10, Z <= 16, ZZ <= 4; Q <= 2 -> (5, 3, 1), or P unchanged.

@@ -13,7 +13,7 @@
 //   dbl_zz  : dbl + ZZ = Z3^2 (4), U2 = x ZZ, T = y Z3 (1)       3 levels
 //   madd_zz : (10, 10, 2) after dbl_zz, (x, y) m <= 2 -> (9, 6, 2)    3 levels
 // The mixed addition has no P = +-Q branches: it runs only inside the GLV chain, where (as the trio
-// kernel's trio_add_digit_zz argues) the accumulator K R with |K| >= 16 can never equal +-d R, |d| <= 8;
+// kernel's trio_glv_chain argues) the accumulator K R with |K| >= 16 can never equal +-d R, |d| <= 8;
 // infinity is the chain's own (wave-uniform) flag.
 #pragma once
 #include "fe26.h"

@@ -1004,8 +1004,10 @@ __device__ __forceinline__ void lds_store_fe26(uint32_t (*dst)[64], const fe26& 
 // The GLV chains of the trio kernel: wave w runs chain w & 1 for txs 20 (w >> 1) .. 20 (w >> 1) + 19
 // of the workgroup, one trio (three adjacent lanes, ec26_trio.h) per tx; lane position p of DPP row r
 // is trio p / 3 (p = 15 a phantom that mirrors trio 4 and stores nothing).
-// The trio kernel's LDS: Coop26Lds without the wave-pair exchange slots, and the co-Z table (and
+// The trio kernels' LDS: Coop26Lds without the wave-pair exchange slots, and the co-Z table (and
 // beta x) kept as canonical fe26 limbs, so a window's lookup is 20 LDS reads and no conversion.
+// Trio26Lds is what both trio kernels use (all of the known-key kernel's); Trio26RecoverLds adds the
+// recovery kernel's own members.
 constexpr int kTrioWords = 31;  // a TrioPt in LDS (trio_store)
 struct Trio26Lds {
     uint32_t tab[8][20][64];          // [entry][x limbs 0..9, y limbs 0..9][tx]
@@ -1019,21 +1021,20 @@ struct Trio26Lds {
     uint32_t ys[8][64];
     uint32_t rflag[64];
     uint32_t post[3];
-    uint32_t invq[2][4];  // phase D: Z^-1 over wave pairs (0, 1) and (2, 3): posted, consumed, d ready
-    // the split square root (BCOSGPU_TRIO_SQRT_SPLIT): the head's live elements and w, raw limbs, from
-    // phase A's wave 2 to phase D's chain-1 waves; and their verdict y^2 = w
+};
+struct Trio26RecoverLds : Trio26Lds {
+    // the split square root: the head's live elements (0..4) and w (5), raw limbs, from phase A's wave 2
+    // to phase D's chain-1 waves; and their verdict y^2 = w
     uint32_t sq[6][10][40];
     uint32_t yok[64];
-    // with the split root no barrier separates the phases up to phase D's last addition (the chain-1 waves,
-    // which leave phase A first, run ahead and sum the comb partials early), so the hand-offs are flags:
+    // no barrier separates the phases up to phase D's last addition (the chain-1 waves, which leave
+    // phase A first, run ahead and sum the comb partials early), so the hand-offs are flags:
     // 0 table, k and flags ready (wave 1); 1 + w: wave w's comb partial stored; 5 + p: wave pair p's chain-1
     // point stored.  The points then cannot reuse the table's LDS: xg holds them ([pair] chain point /
     // sum S / X3 Y3, [2 + pair] the G part).
     uint32_t spost[8];
     uint32_t xg[4][kTrioWords][64];
 };
-// phase D's Z^-1 ring and d (two wave pairs) live in pt, which is free by then
-static_assert(2 * (kInvRing * 4 * 64 + 9 * 64) <= sizeof(Trio26Lds::pt) / 4, "Z^-1 queue exceeds pt");
 __device__ __forceinline__ void lds_store_limbs26(uint32_t (*dst)[64], const fe26& a, int lane) {
     fe26 t;
     fe26_copy(t, a);
@@ -1088,93 +1089,658 @@ __device__ __forceinline__ void trio_entry(Aff26& S, const Trio26Lds& L, int tl,
     fe26_cmov(S.y, ny, (d < 0) != neg);
 }
 
-// A window of a GLV chain, after trio_dbl_zz: acc <- acc + d * (table point), d a Booth digit in [-8, 8],
-// in 4 product levels (trio_madd_zz).  The addition runs without P = Q / P = -Q tests: acc is K R for the
-// digits K processed so far and the table point is |d| R with |d| <= 8; once K != 0 every window makes
-// |K| >= 16 before its addition, so K = +-d (mod n) would need 16 <= |K| <= 8 -- impossible for
-// |K| < 2^130 < n and R of order n.  (An R that is not on the curve fails its verdict and its chain's
-// value is discarded.)  K = 0 is the infinity flag, which the addition handles.  The chain's start
-// (trio_chain_start, ec26_trio.h) adds b <= 1 to K = 2a, a <= 8: 2a = +-b only for a = 0, the flag again.
-// (Reading the table entry before the window's doublings, to take the LDS latency off the first level,
-// measured no gain: 893k cycles either way.)
-__device__ __forceinline__ void trio_add_digit_zz(TrioPt& acc, const Trio26Lds& L, int tl, int d, bool neg, bool phi,
-                                                  const fe26& ZZ, const TrioLane& T) {
-    Aff26 S;
-    trio_entry(S, L, tl, d, neg, phi);
-    TrioPt R;
-    trio_madd_zz(R, acc, ZZ, S, T);
-    trio_cmov(acc, R, d != 0);
+// Phase C of both trio kernels, one GLV chain on a trio: acc = +-k R (chain 0) or +-k phi(R) (chain 1) for
+// the half scalar k = L.k[chain] of tx tl and its sign in tflags (bit 2 / bit 3), on the table's curve.
+// Digits 32 and 31 go together (trio_chain_start), then 31 lean windows (trio_window on a TrioAcc: four
+// doublings and acc <- acc + d * (table point), d a Booth digit in [-8, 8]).  Reads L.k, L.tab and L.tabphx
+// of column tl and writes no LDS; every wave calls it, all lanes of a trio alike.
+// The windows' additions run without P = Q / P = -Q tests: acc is K R for the digits K processed so far and
+// the table point is |d| R with |d| <= 8; once K != 0 every window makes |K| >= 16 before its addition, so
+// K = +-d (mod n) would need 16 <= |K| <= 8 -- impossible for |K| < 2^130 < n and R of order n.  (An R that
+// is not on the curve fails its verdict and its chain's value is discarded.)  K = 0 is the infinity flag,
+// which the addition handles.  The chain's start adds b <= 1 to K = 2a, a <= 8: 2a = +-b only for a = 0, the
+// flag again.  (Reading the table entry before the window's doublings, to take the LDS latency off the
+// first level, measured no gain: 893k cycles either way.)
+__device__ __forceinline__ void trio_glv_chain(TrioPt& acc, const Trio26Lds& L, int chain, int tl, uint32_t tflags,
+                                               const TrioLane& T) {
+    fe k;
+    fe_zero(k);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) k.v[q] = L.k[chain][q][tl];
+    const bool neg = chain == 0 ? (tflags & 4u) != 0 : (tflags & 8u) != 0;
+    const bool phi = chain == 1;
+    // digits 32 and 31 together (16 d32 + d31 = 2a + b): a R from the table, one doubling, b R
+    trio_chain_start(acc, k.v[3], [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
+    shl4_128(k);  // booth_digit128 goes on at digit 30
+    TrioAcc la;
+    trio_acc_from(la, acc);
+#pragma unroll 1
+    for (int w = 30; w >= 0; --w)
+        trio_window(la, booth_digit128(k), [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
+    trio_acc_to(acc, la, T);
 }
 
-// TRIO = false: tx_verify_coop26_kernel (64 txs per workgroup, wave-pair chains); TRIO = true:
-// tx_verify_trio26_kernel (40 txs per workgroup, lane-trio chains).  Phases A and D are the same code.
-// MODE kRecover: public-key recovery (Q = u1 G + u2 R, R from r and v); MODE kVerify (TRIO only):
-// libsecp256k1 ecdsa_verify with a KNOWN key P (sig_verify_trio26_kernel, KeyIO): Q = (e/s) G + (r/s) P,
-// accept iff x(Q) = r mod n -- no square root (P is given), s^-1 instead of r^-1, and the projective
-// x-check instead of the affine inversion and the address hash.
-enum { kRecover = 0, kVerify = 1 };
-#ifndef kTrioDblUnroll
-#define kTrioDblUnroll 3  // phase C doublings per window unrolled (rolled, 1: 0.385 vs 0.383 ms)
-#endif
-// Phase C's windows: 1 the lean window (trio_window, ec26_trio.h: the same 16 product levels with fewer routing
-// and small-constant instructions between them), 0 the earlier one (trio_dbl x 3, trio_dbl_zz,
-// trio_add_digit_zz; A/B).  The chain start is the same for both.
-#ifndef BCOSGPU_TRIO_WINDOW
-#define BCOSGPU_TRIO_WINDOW 1
-#endif
-#ifndef BCOSGPU_TRIO_INV_SPLIT
-#define BCOSGPU_TRIO_INV_SPLIT 1  // phase-D Z^-1 over wave pairs (0 = the one-wave pipelined loop, A/B)
-#endif
-// The trio kernel's recovery square root y = w^((p+1)/4) cut in two (fe26_sqrt_head / fe26_sqrt_tail): wave 2
-// runs the head in phase A and then takes comb windows like the other waves; the chain-1 waves run the
-// tail in phase D, beside the Z^-1 of the chain-0 waves, whose input does not depend on y.
-// 0: the whole root in phase A (the earlier schedule); 1: cut after x176 (tail 78 S + 4 M; Z^-1 on one
-// wave, its partner being busy); 2: cut after x223 (tail 31 S + 2 M; Z^-1 as BCOSGPU_TRIO_INV_SPLIT says).
-#ifndef BCOSGPU_TRIO_SQRT_SPLIT
-#define BCOSGPU_TRIO_SQRT_SPLIT 1
-#endif
-// with the split root: the first comb window of waves 3, 2 and 1 (wave 0 starts at 0; of the 16 windows of
-// the 16-bit comb, doubled for the 8-bit comb); a wave with no window adds no partial in phase D
-#ifndef BCOSGPU_TRIO_SPLIT_WIN
-#if BCOSGPU_TRIO_SQRT_SPLIT == 2
-#define BCOSGPU_TRIO_SPLIT_WIN 7, 14, 14
-#else
-#define BCOSGPU_TRIO_SPLIT_WIN 7, 13, 16
-#endif
-#endif
-template <bool TRIO, int MODE, class IO>
-__device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint32_t* __restrict__ tab, int tab_bits) {
-    static_assert(MODE == kRecover || TRIO, "known-key verify runs on the trio kernel only");
-    constexpr bool kVer = MODE == kVerify;
-    constexpr int TPW = TRIO ? 40 : 64;  // txs per workgroup
-    constexpr bool kSplit = TRIO && !kVer && BCOSGPU_TRIO_SQRT_SPLIT != 0;  // the square root's tail in phase D
-    constexpr int kCut = BCOSGPU_TRIO_SQRT_SPLIT == 2 ? 1 : 0, kLive = fe26_sqrt_live<kCut>();
-    constexpr int kSw[3] = {BCOSGPU_TRIO_SPLIT_WIN};
-    static_assert(0 < kSw[0] && kSw[0] < kSw[1] && kSw[1] <= kSw[2] && kSw[2] <= 16, "comb windows of waves 0, 3, 2, 1");
-    __shared__ std::conditional_t<TRIO, Trio26Lds, Coop26Lds> L;
+// The sum of phase A's comb partials on a chain-1 wave of a trio kernel, as a trio point: pt[3] + pt[4]
+// (+ pt[0], + pt[2]) of column tl.  Reads L.pt, which the caller has made visible (flags or a barrier),
+// and writes no LDS.
+template <bool WITH0, bool WITH2>
+__device__ __forceinline__ void trio_sum_partials(TrioPt& A, const Trio26Lds& L, int tl, const TrioLane& T) {
+    Jac26 Ga, Gb;
+    TrioPt B;
+    coop26_load_jac(Ga, L.pt[3], tl);
+    coop26_load_jac(Gb, L.pt[4], tl);
+    trio_from_jac(A, Ga, T);
+    trio_from_jac(B, Gb, T);
+    trio_add(A, A, B, T);
+    if constexpr (WITH0) {
+        coop26_load_jac(Gb, L.pt[0], tl);
+        trio_from_jac(B, Gb, T);
+        trio_add(A, A, B, T);
+    }
+    if constexpr (WITH2) {
+        coop26_load_jac(Gb, L.pt[2], tl);
+        trio_from_jac(B, Gb, T);
+        trio_add(A, A, B, T);
+    }
+}
+
+// ------------------------------------------------------------------ the three fe26 kernels
+// One body per kernel, phases shared as the functions below and above:
+//   coop26_body          tx_verify_coop26_kernel   recovery, 64 txs per workgroup, wave-pair chains
+//   trio26_recover_body  tx_verify_trio26_kernel   recovery, 40 txs per workgroup, lane-trio chains, the
+//                                                  square root split between phase A and phase D
+//   trio26_verify_body   sig_verify_trio26_kernel  libsecp256k1 ecdsa_verify with a KNOWN key P (KeyIO) on
+//                                                  lane trios: Q = (e/s) G + (r/s) P, accept iff x(Q) = r mod n
+// Recovery computes Q = u1 G + u2 R with R from r and v; known-key verify needs no square root (P is
+// given), s^-1 instead of r^-1, and the projective x-check instead of the affine inversion and the
+// address hash.  Shared: recover_w (both recoveries), coop26_table_to_lds and the scalar phase
+// (coop26_post_e_inv, coop26_u1_glv; all three), comb_share (all three), trio_glv_chain and
+// trio_sum_partials (both trio kernels); trio_recover_tail names the recovery kernel's last phase.
+
+// Recovery, waves 1 and 2: X = r (+ n when v & 2) as fe26 and w = X^3 + 7 (m 2); returns ok and, for
+// v & 2, r < p - n.  No LDS.
+__device__ __forceinline__ bool recover_w(fe26& X, fe26& w, const fe& r, uint32_t v, bool ok) {
+    fe x;
+    fe_copy(x, r);
+    bool okr = ok;
+    if (v & 2u) {
+        okr = okr && fe_lt_k(r, kK1PminusN);
+        fe_add_k(x, r, ParamN1::M);
+    }
+    fe26 t, seven;
+    fe26_from_fe(X, x);
+    fe26_sqr(t, X);
+    fe26_mul(w, t, X);
+    fe26_set_small(seven, 7u);
+    fe26_add(w, w, seven);
+    return okr;
+}
+
+// The co-Z table of P -- 1 P .. 8 P over one Z (coz_table26) -- into L.tab, beta * x of each entry into
+// L.tabphx and that Z into L.zc, column `lane`.  LIMBS: the trio kernels' layout (canonical fe26 limbs, 10 +
+// 10 rows per entry); else the pair kernel's (canonical 8-word values, 8 + 8 rows).  Reads no LDS.  Wave 1
+// calls it: with the key in trio26_verify_body, with R' = (w x, w^2) in the two recovery bodies.
+template <bool LIMBS, class LDS>
+__device__ __forceinline__ void coop26_table_to_lds(LDS& L, const Aff26& P, int lane) {
+    Aff26 A[8];
+    fe26 Zc, beta;
+    {
+        Jac26 T[8];
+        multiples8_26(T, P);
+        coz_table26(A, Zc, T);
+    }
+    fe26_const(beta, kGlvBeta);
+    Unroll<0, 8>::run([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        fe26 bx;
+        fe26_mul(bx, A[j].x, beta);
+        if constexpr (LIMBS) {
+            lds_store_limbs26(L.tab[j], A[j].x, lane);
+            lds_store_limbs26(L.tab[j] + 10, A[j].y, lane);
+            lds_store_limbs26(L.tabphx[j], bx, lane);
+        } else {
+            lds_store_fe26(L.tab[j], A[j].x, lane);
+            lds_store_fe26(L.tab[j] + 8, A[j].y, lane);
+            lds_store_fe26(L.tabphx[j], bx, lane);
+        }
+    });
+    lds_store_fe26(L.zc, Zc, lane);
+}
+
+// The scalar phase's producers, called by all four waves (VERIFY: known-key verify, else recovery).  Wave 3:
+// e = digest mod n into L.xe, posts L.post[1].  Wave 0: r^-1 (VERIFY: s^-1) mod n, Montgomery form, into
+// L.xrinv, posts L.post[0]; PIPE takes the pipelined inversion (the trio kernels have the registers).
+// Rejected lanes get r = 1, s = 0 (VERIFY: 1) first, which keeps the arithmetic well defined.
+template <bool VERIFY, bool PIPE, class LDS, class IO>
+__device__ __forceinline__ void coop26_post_e_inv(LDS& L, const IO& io, uint64_t i, bool active, bool ok, fe& r, fe& s,
+                                                  int wave, int lane) {
+    if (!ok) {
+        fe_zero(r);
+        r.v[0] = 1;
+        fe_zero(s);
+        if (VERIFY) s.v[0] = 1;
+    }
+    if (wave == 3) {
+        fe e;
+        fe_zero(e);
+        if (active) io.template digest<KECCAK256>(i, e);
+        reduce_once(e, ParamN1::M);
+        lds_store_fe(L.xe, e, lane);
+        coop_post(&L.post[1]);
+        COOP_T(7);
+    } else if (wave == 0) {
+        fe rm, rinv;
+        FieldN1::from_plain(rm, VERIFY ? s : r);
+        if constexpr (PIPE) FieldInv<FieldN1>::inv_pipe(rinv, rm);
+        else FieldInv<FieldN1>::inv(rinv, rm);
+        lds_store_fe(L.xrinv, rinv, lane);
+        coop_post(&L.post[0]);
+        COOP_T(7);
+    }
+}
+// The scalar phase's consumers: waits for L.post[0] and L.post[1], then u1 = -e / r (VERIFY: e / s) for the
+// caller's comb windows; wave 1 also takes u2 = s / r (VERIFY: r / s), splits it (glv_split) and leaves the
+// halves in L.k and L.flags = ok | neg1 << 2 | neg2 << 3.  Every wave that takes comb windows calls it.
+template <bool VERIFY, class LDS>
+__device__ __forceinline__ void coop26_u1_glv(fe& u1, LDS& L, bool ok, const fe& r, const fe& s, int wave, int lane) {
+    coop_wait(&L.post[0]);
+    coop_wait(&L.post[1]);
+    fe e, rinv;
+    lds_load_fe(e, L.xe, lane);
+    lds_load_fe(rinv, L.xrinv, lane);
+    FieldN1::mul(u1, e, rinv);
+    if (!VERIFY) FieldN1::neg(u1, u1);
+    if (wave == 1) {
+        fe u2, k1, k2;
+        FieldN1::mul(u2, VERIFY ? r : s, rinv);
+        bool neg1, neg2;
+        glv_split(k1, neg1, k2, neg2, u2);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            L.k[0][q][lane] = k1.v[q];
+            L.k[1][q][lane] = k2.v[q];
+        }
+        L.flags[lane] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
+    }
+}
+
+// Which comb windows [lo, hi) of u1 G a wave takes in phase A: one table per kernel, [wave] -> {lo, hi}, on
+// the 16-bit comb's 16 windows (wide) and on the 8-bit comb's 32 (narrow).  comb_share reads a row as selects
+// (the compiler does not know that `wave` is uniform).
+struct CombShare {
+    int wide[4][2], narrow[4][2];
+};
+__device__ __forceinline__ void comb_share(int& lo, int& hi, const int (&t)[4][2], int wave) {
+    lo = t[0][0];
+    hi = t[0][1];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        if (wave == w) {
+            lo = t[w][0];
+            hi = t[w][1];
+        }
+    }
+}
+// the windows of `wave` on whichever comb tab_bits names (both trio kernels)
+__device__ __forceinline__ void comb_share_range(Jac26& G, const fe& u1, const uint32_t* __restrict__ tab, int tab_bits,
+                                                 const CombShare& share, int wave) {
+    int lo, hi;
+    if (tab_bits == kWideBits) {
+        comb_share(lo, hi, share.wide, wave);
+        comb_range26w<kWideBits>(G, u1, tab, lo, hi);
+    } else {
+        comb_share(lo, hi, share.narrow, wave);
+        comb_range26w<8>(G, u1, tab, lo, hi);
+    }
+}
+// The pair kernel (always on the 8-bit comb; wave 2 takes the square root): 12 / 12 / 8 to waves 0 / 3 / 1.
+constexpr int kPairShare[4][2] = {{0, 12}, {24, 32}, {0, 0}, {12, 24}};
+// Recovery on trios: waves 0 / 3 / 2 / 1 take windows [0, a) / [a, b) / [b, c) / [c, 16) of kTrioSplitWin =
+// a, b, c, doubled on the 8-bit comb: 7 / 6 / 3 / 0 (wave 2 joins after the root's head, wave 1 after the
+// table and the GLV split).  A wave with no window adds no partial in phase D.
+constexpr int kTrioSplitWin[3] = {7, 13, 16};
+static_assert(0 < kTrioSplitWin[0] && kTrioSplitWin[0] < kTrioSplitWin[1] && kTrioSplitWin[1] <= kTrioSplitWin[2] &&
+                  kTrioSplitWin[2] <= 16,
+              "comb windows of waves 0, 3, 2, 1");
+constexpr CombShare trio_recover_share() {
+    const int a = kTrioSplitWin[0], b = kTrioSplitWin[1], c = kTrioSplitWin[2];
+    return {{{0, a}, {c, 16}, {b, c}, {a, b}}, {{0, 2 * a}, {2 * c, 32}, {2 * b, 2 * c}, {2 * a, 2 * b}}};
+}
+constexpr CombShare kTrioRecoverShare = trio_recover_share();
+// Known-key verify: 6 / 4 / 5 / 1 to waves 0 / 3 / 2 / 1 (wave 1 builds the table first; wave 3 also adds wave
+// 0's partial), 11 / 8 / 11 / 2 on the 8-bit comb.
+constexpr CombShare kTrioVerifyShare = {{{0, 6}, {15, 16}, {10, 15}, {6, 10}}, {{0, 11}, {30, 32}, {19, 30}, {11, 19}}};
+
+// Phase A's first hand-over of comb partials (the pair kernel and known-key verify): wave 0 leaves its
+// partial in L.pt[2] behind L.post[2]; wave 3 adds it to its own (G0 + G3 while phase A waits for wave 1's
+// last window: one addition off phase D) into L.pt[3]; wave 1's goes to L.pt[4], wave 2's to L.pt[0].
+template <class LDS>
+__device__ __forceinline__ void coop26_store_partial(LDS& L, const Jac26& G, int wave, int lane) {
+    if (wave == 0) {
+        coop26_store_jac(L.pt[2], G, lane);
+        coop_post(&L.post[2]);
+    } else if (wave == 3) {
+        Jac26 G0, S;
+        coop_wait(&L.post[2]);
+        coop26_load_jac(G0, L.pt[2], lane);
+        CurveK1x::add(S, G0, G);
+        coop26_store_jac(L.pt[3], S, lane);
+    } else {
+        coop26_store_jac(L.pt[wave == 1 ? 4 : 0], G, lane);
+    }
+}
+
+// tx_verify_coop26_kernel: recovery with each GLV chain on a wave pair (chain = wave >> 1, role = wave & 1).
+// Phase A: wave 1 the table of R', wave 2 the square root, wave 3 the digest, wave 0 r^-1, then the comb
+// windows on waves 0, 3 and 1; a barrier; phase C; a barrier; phase D on waves 1 and 0, then on wave 0 alone.
+template <class IO>
+__device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint32_t* __restrict__ tab) {
+    __shared__ Coop26Lds L;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * TPW + lane;
-    const bool active = lane < TPW && i < n;
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 64 + lane;
+    const bool active = i < n;
     COOP_T(0);
     if (threadIdx.x == 0) {
         L.post[0] = 0u;
         L.post[1] = 0u;
         L.post[2] = 0u;
-        if constexpr (TRIO) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) (&L.invq[0][0])[q] = 0u;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) L.spost[q] = 0u;
-        }
     }
     __syncthreads();
     // ---------------------------------------------------------------- phase A (as tx_verify_coop_kernel)
     fe r, s;
     uint32_t v = 0;
     bool ok = false;
-    if constexpr (kVer) {
-        // verify: wave 1 checks the key and builds ITS table (P is given: no square root); r kept for the
-        // final x-check (in the LDS slot recovery uses for y)
+    if (active) ok = io.rsv(i, r, s, v);
+    else { fe_zero(r); fe_zero(s); }
+    if (wave == 1 || wave == 2) {
+        fe26 X, rhs;
+        bool okr = recover_w(X, rhs, r, v, ok);
+        if (wave == 2) {
+            fe26 y, ny, t;
+            fe26_sqrt_cand(y, rhs);
+            fe26_sqr(t, y);
+            fe26_sub<3>(t, t, rhs);
+            okr = okr && fe26_is_zero(t);
+            fe26_normalize(y);
+            fe26_neg<2>(ny, y);
+            fe26_normalize(ny);
+            fe26_cmov(y, ny, (y.v[0] & 1u) != (v & 1u));
+            lds_store_fe26(L.ys, y, lane);
+            L.rflag[lane] = okr ? 2u : 0u;
+            COOP_T(6);
+        } else {
+            Aff26 R;
+            fe26_mul(R.x, rhs, X);  // w x
+            fe26_sqr(R.y, rhs);     // w^2
+            coop26_table_to_lds<false>(L, R, lane);
+            COOP_T(6);
+        }
+    }
+    coop26_post_e_inv<false, false>(L, io, i, active, ok, r, s, wave, lane);
+    if (wave != 2) {
+        fe u1;
+        coop26_u1_glv<false>(u1, L, ok, r, s, wave, lane);
+        Jac26 G;
+        int lo, hi;
+        comb_share(lo, hi, kPairShare, wave);
+        comb_range26w<8>(G, u1, tab, lo, hi);
+        coop26_store_partial(L, G, wave, lane);
+    }
+    COOP_T(1);
+    __syncthreads();
+    // ---------------------------------------------------------------- phase C: two cooperative GLV chains
+    const uint32_t flags = L.flags[lane] | L.rflag[lane];
+    {
+        Coop26Ctx c{&L, wave >> 1, wave & 1, lane, false};
+        fe k;
+        fe_zero(k);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) k.v[q] = L.k[c.chain][q][lane];
+        const bool neg = c.chain == 0 ? (flags & 4u) != 0 : (flags & 8u) != 0;
+        const bool phi = c.chain == 1;
+        Jac26 acc;
+        CurveK1x::set_inf(acc);
+        coop26_add_digit(acc, c, static_cast<int>(k.v[3] >> 31), neg, phi);  // digit 32 = bit 127
+#pragma unroll 1
+        for (int w = 31; w >= 0; --w) {
+            coop26_dbl<0>(acc, c);
+#ifdef BCOSGPU_COOP_TIMING
+            c.probe = blockIdx.x == 0 && w == 20;
+#endif
+            coop26_dbl<3>(acc, c);
+#ifdef BCOSGPU_COOP_TIMING
+            c.probe = false;
+            if (blockIdx.x == 0 && w == 20 && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][5] = clock64();
+#endif
+            coop26_dbl<0>(acc, c);
+            coop26_dbl<3>(acc, c);
+#ifdef BCOSGPU_COOP_TIMING
+            if (blockIdx.x == 0 && w == 20 && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][6] = clock64();
+#endif
+            coop26_add_digit(acc, c, booth_digit128(k), neg, phi);
+#ifdef BCOSGPU_COOP_TIMING
+            if (blockIdx.x == 0 && w == 20 && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][7] = clock64();
+#endif
+        }
+        COOP_T(2);
+        if (c.role == 0) coop26_store_jac(L.pt[c.chain], acc, lane);
+    }
+    __syncthreads();
+    // ---------------------------------------------------------------- phase D (on fe26 as well)
+    if (wave == 1) {  // G part: (partials 0 + 1, phase A) + 2
+        Jac26 G01, G2, U;
+        coop26_load_jac(G01, L.pt[3], lane);
+        coop26_load_jac(G2, L.pt[4], lane);
+        CurveK1x::add(U, G01, G2);
+        coop26_store_jac(L.pt[2], U, lane);
+    } else if (wave == 0) {  // R part: co-Z curve -> E_w (Z * Zc) -> E (Z * y)
+        Jac26 P0, P1, Q;
+        coop26_load_jac(P0, L.pt[0], lane);
+        coop26_load_jac(P1, L.pt[1], lane);
+        fe26 Zc, y;
+        lds_load_fe26(Zc, L.zc, lane);
+        lds_load_fe26(y, L.ys, lane);
+        CurveK1x::add(Q, P0, P1);
+        fe26_mul(Zc, Zc, y);
+        fe26_mul(Q.Z, Q.Z, Zc);
+        coop26_store_jac(L.pt[0], Q, lane);
+    }
+    __syncthreads();
+    if (wave == 0 && active) {
+        Jac26 Q, G, R;
+        coop26_load_jac(Q, L.pt[0], lane);
+        coop26_load_jac(G, L.pt[2], lane);
+        CurveK1x::add(R, Q, G);
+        const bool ok2 = (flags & 3u) == 3u && !R.inf;
+        COOP_T(4);
+        fe z, zi, ax, ay;
+        fe26_to_fe(z, R.Z);
+        FieldInv<FieldK1>::inv(zi, z);
+        COOP_T(5);
+        fe26 zi26, zi2, zi3, X, Y;
+        fe26_from_fe(zi26, zi);
+        fe26_sqr(zi2, zi26);
+        fe26_mul(X, R.X, zi2);
+        fe26_mul(zi3, zi2, zi26);
+        fe26_mul(Y, R.Y, zi3);
+        fe26_to_fe(ax, X);
+        fe26_to_fe(ay, Y);
+        uint32_t ad[5] = {0, 0, 0, 0, 0};
+        if (ok2 && io.want_addr()) keccak_address(ad, ax, ay);
+        io.finish(i, ok2, ad, &ax, &ay);
+    }
+    COOP_T(3);
+}
+
+// ------------------------------------------------------------------ the lane-trio kernels
+// Phase C's doublings and mixed additions cost one multiplication of latency per dependency level with DPP
+// exchanges inside a wave instead of LDS exchanges and barriers between waves, and 40 txs per workgroup
+// spread a 10k batch over 250 CUs instead of 157.  Wave w runs chain w & 1 of txs 20 (w >> 1) .. + 19.
+constexpr int kTrioTxs = 40;  // txs per workgroup
+// where a lane stands in phase C and after: its trio's tx column tl of the workgroup (lane position 15 of a
+// DPP row is a phantom that mirrors trio 4) and whether it is the trio's lane 2 of a real trio
+struct TrioSeat {
+    int chain, tl;
+    bool real;
+    __device__ __forceinline__ TrioSeat(int wave, int lane, const TrioLane& T) {
+        const int trio_idx = (lane & 15) / 3;
+        chain = wave & 1;
+        tl = (wave >> 1) * 20 + (lane >> 4) * 5 + (trio_idx < 5 ? trio_idx : 4);
+        real = T.r2 && trio_idx < 5;
+    }
+};
+
+// The recovery kernel's last phase, called by all four waves after the barrier behind which mbuf holds
+// x || y of every tx ([40][16] big-endian words): Keccak256 of it on lane PAIRS (KeccakPair) of the chain-0
+// waves, tx j = lane / 2 of the wave, the digests to mbuf + 640 ([40][8]); a barrier; then lane 2 of each
+// real trio of the chain-0 waves takes right160 of its tx's digest and calls io.finish.
+template <class IO>
+__device__ __forceinline__ void trio_recover_tail(const IO& io, uint32_t* mbuf, int wave, int lane, const TrioSeat& seat,
+                                                  uint64_t ti, bool tactive, bool ok2, const fe& ax, const fe& ay) {
+    if (seat.chain == 0 && io.want_addr()) {
+        const KeccakPair kp;
+        const int j = lane >> 1, t = (wave >> 1) * 20 + (j < 20 ? j : 0);
+        uint32_t d[4];
+        kp.hash(reinterpret_cast<const uint8_t*>(mbuf + 16 * t), 64u, d);
+        if (j < 20) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mbuf[640 + 8 * t + 2 * q + (lane & 1)] = d[q];
+        }
+    }
+    __syncthreads();
+    if (seat.chain == 0 && seat.real && tactive) {
+        uint32_t ad[5] = {0, 0, 0, 0, 0};
+        if (ok2 && io.want_addr()) {
+#pragma unroll
+            for (int q = 0; q < 5; ++q) ad[q] = mbuf[640 + 8 * seat.tl + 3 + q];  // right160
+        }
+        io.finish(ti, ok2, ad, &ax, &ay);
+    }
+}
+
+// tx_verify_trio26_kernel.  The recovery square root y = w^((p+1)/4) is cut in two after x176
+// (fe26_sqrt_head<0> / fe26_sqrt_tail<0>): wave 2 runs the head in phase A and then takes comb windows like
+// the other waves; the chain-1 waves run the tail (78 S + 4 M) in phase D, beside the Z^-1 of the chain-0
+// waves, whose input does not depend on y.  No barrier separates the phases up to phase D's
+// last addition: the hand-offs are the flags of Trio26RecoverLds::spost.
+template <class IO>
+__device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, const uint32_t* __restrict__ tab,
+                                                    int tab_bits) {
+    constexpr int kLive = fe26_sqrt_live<0>();
+    constexpr bool kWave2Adds = kTrioSplitWin[1] < kTrioSplitWin[2], kWave1Adds = kTrioSplitWin[2] < 16;
+    __shared__ Trio26RecoverLds L;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + lane;
+    const bool active = lane < kTrioTxs && i < n;
+    COOP_T(0);
+    if (threadIdx.x == 0) {
+        L.post[0] = 0u;
+        L.post[1] = 0u;
+        L.post[2] = 0u;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) L.spost[q] = 0u;
+    }
+    __syncthreads();
+    // ---------------------------------------------------------------- phase A
+    fe r, s;
+    uint32_t v = 0;
+    bool ok = false;
+    if (active) ok = io.rsv(i, r, s, v);
+    else { fe_zero(r); fe_zero(s); }
+    if (wave == 1 || wave == 2) {
+        fe26 X, rhs;
+        const bool okr = recover_w(X, rhs, r, v, ok);
+        if (wave == 2) {  // the root's head only; the verdict so far, and v's parity for the tail
+            fe26 st[kLive];
+            fe26_sqrt_head<0>(st, rhs);
+            if (lane < kTrioTxs) {
+#pragma unroll
+                for (int j = 0; j < kLive; ++j) {
+#pragma unroll
+                    for (int q = 0; q < 10; ++q) L.sq[j][q][lane] = st[j].v[q];
+                }
+#pragma unroll
+                for (int q = 0; q < 10; ++q) L.sq[5][q][lane] = rhs.v[q];
+            }
+            L.rflag[lane] = (okr ? 2u : 0u) | ((v & 1u) << 4);
+            COOP_T(6);
+        } else {
+            Aff26 R;
+            fe26_mul(R.x, rhs, X);  // w x
+            fe26_sqr(R.y, rhs);     // w^2
+            coop26_table_to_lds<true>(L, R, lane);
+            COOP_T(6);
+        }
+    }
+    coop26_post_e_inv<false, true>(L, io, i, active, ok, r, s, wave, lane);
+    {
+        fe u1;
+        coop26_u1_glv<false>(u1, L, ok, r, s, wave, lane);
+        if (wave == 1) coop_post(&L.spost[0]);  // phase C may start: the table, Zc, k and the flags
+        Jac26 G;
+        int lo, hi;
+        comb_share(lo, hi, kTrioRecoverShare.wide, wave);
+        if (lo == hi) CurveK1x::set_inf(G);
+        else comb_share_range(G, u1, tab, tab_bits, kTrioRecoverShare, wave);
+        // no partial is added here: each wave's goes to phase D behind its own flag
+        coop26_store_jac(L.pt[wave == 0 ? 3 : wave == 3 ? 4 : wave == 2 ? 0 : 2], G, lane);
+        coop_post(&L.spost[1 + wave]);
+    }
+    COOP_T(1);
+    // each wave enters phase C once wave 1 has posted the table and the scalars; what the other waves leave
+    // in LDS is read in phase D only, behind their own flags or a barrier
+    coop_wait(&L.spost[0]);
+    // ---------------------------------------------------------------- phase C: one GLV chain per trio
+    const TrioLane T(lane);
+    const TrioSeat seat(wave, lane, T);
+    const int chain = seat.chain, tl = seat.tl;
+    const uint32_t tflags = L.flags[tl];  // (wave 2's rflag is read in phase D, behind a barrier)
+    TrioPt acc;
+    trio_glv_chain(acc, L, chain, tl, tflags, T);
+    COOP_T(2);
+    // ---------------------------------------------------------------- phase D on the trios
+    // The chains' sum S lies on E_w; with l = Zc y and K = l^2 = Zc^2 w it is the point (X K, Y K l, Z K) of E
+    // (trio_scale_xz, trio_scale_y), whose X and Z hold no y.  So the Z of the last addition T + S_E (T the G
+    // part) needs no y: chain 0 computes it alone (trio_add_z) and starts Z^-1, while chain 1 finishes the
+    // root, runs the complete addition and hands over X3, Y3.  Chain 1's waves leave phase A, and so phase
+    // C, before chain 0's: they sum the comb partials in that lead, behind flags instead of barriers.  All
+    // additions are trio_add (6 product levels instead of 16 products on one lane).  Then the affine map
+    // on lane 2 of each trio, and trio_recover_tail.
+    uint32_t* const xbuf = &L.xg[wave >> 1][0][0];
+    uint32_t* const gbuf = &L.xg[2 + (wave >> 1)][0][0];
+    uint32_t* const mbuf = &L.tabphx[0][0][0];  // [40][16] pubkey messages, then [40][8] digests
+    const uint64_t ti = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + tl;
+    const bool tactive = ti < n;
+    fe ax, ay;
+    bool ok2 = false;
+    const auto load_zc_w = [&](fe26& zc, fe26& w) {
+        lds_load_fe26(zc, L.zc, tl);
+#pragma unroll
+        for (int q = 0; q < 10; ++q) w.v[q] = L.sq[5][q][tl];
+        F26_SETM(w, 2);
+    };
+    TrioPt SE;
+    fe26 zi2, zi3;  // chain 0: Z^-2, Z^-3
+    fe26_zero(zi2);
+    fe26_zero(zi3);
+    if (chain == 1) {  // its chain's point to the partner; T = the sum of phase A's comb partials
+        trio_store(xbuf, acc, lane);
+        coop_post(&L.spost[5 + (wave >> 1)]);
+        coop_wait(&L.spost[1 + 0]);
+        coop_wait(&L.spost[1 + 3]);
+        if constexpr (kWave2Adds) coop_wait(&L.spost[1 + 2]);
+        if constexpr (kWave1Adds) coop_wait(&L.spost[1 + 1]);
+        TrioPt A;
+        trio_sum_partials<kWave2Adds, kWave1Adds>(A, L, tl, T);
+        trio_store(gbuf, A, lane);
+    } else {  // S = k1 R' + k2 phi(R') for the partner, and its X K, Z K here
+        TrioPt P1;
+        coop_wait(&L.spost[5 + (wave >> 1)]);
+        trio_load(P1, xbuf, lane);
+        trio_add(acc, acc, P1, T);
+        trio_store(xbuf, acc, lane);
+        fe26 zc, w, K;
+        coop_wait(&L.spost[1 + 2]);  // w is wave 2's (stored before its comb partial)
+        load_zc_w(zc, w);
+        fe26_sqr(K, zc);
+        fe26_mul(K, K, w);
+        trio_scale_xz(SE, acc, K, T);
+    }
+    __syncthreads();  // every wave is past phase C and phase A; S and T are in LDS
+    const uint32_t rfl = L.rflag[tl];
+    if (chain == 0) {
+        TrioPt G;
+        trio_load(G, gbuf, lane);
+        fe26 Z3;
+        trio_add_z(Z3, G, SE, T);
+        COOP_T(4);
+        fe z, zi;
+        fe26_to_fe(z, Z3);
+        FieldInv<FieldK1>::inv_pipe(zi, z);  // (on one wave: its partner is busy with the root's tail)
+        COOP_T(5);
+        fe26 zi26;
+        fe26_from_fe(zi26, zi);
+        fe26_sqr(zi2, zi26);
+        fe26_mul(zi3, zi2, zi26);
+    } else {
+        TrioPt S, G;
+        trio_load(S, xbuf, lane);
+        trio_load(G, gbuf, lane);
+        fe26 y, ny, t, zc, w, K, l;
+        load_zc_w(zc, w);
+        fe26_sqr(K, zc);
+        fe26_mul(K, K, w);
+        trio_scale_xz(SE, S, K, T);  // (before the tail: less work between y and the hand-over)
+        {
+            fe26 st[kLive];
+#pragma unroll
+            for (int j = 0; j < kLive; ++j) {
+#pragma unroll
+                for (int q = 0; q < 10; ++q) st[j].v[q] = L.sq[j][q][tl];
+                F26_SETM(st[j], 1);
+            }
+            fe26_sqrt_tail<0>(y, st);
+        }
+        fe26_sqr(t, y);
+        fe26_sub<3>(t, t, w);
+        const bool on = fe26_is_zero(t);  // y^2 = w: r is the x of a curve point
+        fe26_normalize(y);
+        fe26_neg<2>(ny, y);
+        fe26_normalize(ny);
+        fe26_cmov(y, ny, (y.v[0] & 1u) != ((rfl >> 4) & 1u));
+        COOP_T(4);
+        fe26_mul(l, zc, y);
+        trio_scale_y(SE, l, T);
+        trio_add(S, G, SE, T);  // T first: S_E = T doubles T, which holds no y
+        trio_store(xbuf, S, lane);
+        if (seat.real) L.yok[tl] = on ? 1u : 0u;
+        COOP_T(5);
+    }
+    __syncthreads();  // X3, Y3 and the verdicts are in LDS
+    if (chain == 0) {
+        TrioPt O;
+        trio_load(O, xbuf, lane);
+        ok2 = (tflags & 1u) != 0u && (rfl & 2u) != 0u && L.yok[tl] != 0u && !O.inf;
+        fe26 X, Y;  // lane 2 holds X3 (Xs), Y3 (S1)
+        fe26_mul(X, O.Xs, zi2);
+        fe26_mul(Y, O.S1, zi3);
+        fe26_to_fe(ax, X);
+        fe26_to_fe(ay, Y);
+        if (seat.real) {
+            uint32_t m[16];
+            fe_to_be_words(m, ax);
+            fe_to_be_words(m + 8, ay);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) mbuf[16 * tl + q] = m[q];
+        }
+    }
+    __syncthreads();
+    trio_recover_tail(io, mbuf, wave, lane, seat, ti, tactive, ok2, ax, ay);
+    COOP_T(3);
+}
+
+// sig_verify_trio26_kernel.  Phase A: wave 1 checks the key and builds ITS table, wave 3 the digest, wave 0
+// s^-1, then the comb windows on all four waves; a barrier; phase C; then phase D between barriers: chain 0
+// (waves 0, 2) takes chain 1's point through LDS and adds it, maps to E (Z Zc: the co-Z table of P itself)
+// and adds the G part, which chain 1 (waves 1, 3) sums meanwhile from phase A's comb partials; the buffers
+// reuse the table's LDS once every wave is past phase C.  The verdict is the projective x-check on lane 2.
+__device__ __forceinline__ void trio26_verify_body(const KeyIO& io, uint64_t n, const uint32_t* __restrict__ tab,
+                                                   int tab_bits) {
+    __shared__ Trio26Lds L;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + lane;
+    const bool active = lane < kTrioTxs && i < n;
+    COOP_T(0);
+    if (threadIdx.x == 0) {
+        L.post[0] = 0u;
+        L.post[1] = 0u;
+        L.post[2] = 0u;
+    }
+    __syncthreads();
+    // ---------------------------------------------------------------- phase A
+    fe r, s;
+    bool ok = false;
+    {
         fe kx, ky;
         if (active) {
             io.key_rs(i, r, s, kx, ky);
@@ -1186,7 +1752,7 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
             fe_zero(kx);
             fe_zero(ky);
         }
-        if (wave == 0) lds_store_fe(L.ys, r, lane);
+        if (wave == 0) lds_store_fe(L.ys, r, lane);  // r kept for the final x-check
         if (wave == 1) {
             Aff26 P;
             fe26_from_fe(P.x, kx);
@@ -1204,602 +1770,92 @@ __device__ __forceinline__ void coop26_body(const IO& io, uint64_t n, const uint
                 fe26_const(P.y, kK1Gy);
             }
             L.rflag[lane] = on ? 2u : 0u;
-            Aff26 A[8];
-            fe26 Zc, beta;
-            {
-                Jac26 T[8];
-                multiples8_26(T, P);
-                coz_table26(A, Zc, T);
-            }
-            fe26_const(beta, kGlvBeta);
-            Unroll<0, 8>::run([&](auto J) {
-                constexpr int j = decltype(J)::value;
-                fe26 bx;
-                fe26_mul(bx, A[j].x, beta);
-                lds_store_limbs26(L.tab[j], A[j].x, lane);
-                lds_store_limbs26(L.tab[j] + 10, A[j].y, lane);
-                lds_store_limbs26(L.tabphx[j], bx, lane);
-            });
-            lds_store_fe26(L.zc, Zc, lane);
-            COOP_T(6);
-        }
-    } else {
-        if (active) ok = io.rsv(i, r, s, v);
-        else { fe_zero(r); fe_zero(s); }
-    }
-    if (!kVer && (wave == 1 || wave == 2)) {
-        fe x;
-        fe_copy(x, r);
-        bool okr = ok;
-        if (v & 2u) {
-            okr = okr && fe_lt_k(r, kK1PminusN);
-            fe_add_k(x, r, ParamN1::M);
-        }
-        fe26 X, rhs, t, seven;
-        fe26_from_fe(X, x);
-        fe26_sqr(t, X);
-        fe26_mul(rhs, t, X);
-        fe26_set_small(seven, 7u);
-        fe26_add(rhs, rhs, seven);  // w (m 2)
-        if (wave == 2 && kSplit) {
-            if constexpr (kSplit) {  // the head only; the verdict so far, and v's parity for the tail
-                fe26 st[kLive];
-                fe26_sqrt_head<kCut>(st, rhs);
-                if (lane < TPW) {
-#pragma unroll
-                    for (int j = 0; j < kLive; ++j) {
-#pragma unroll
-                        for (int q = 0; q < 10; ++q) L.sq[j][q][lane] = st[j].v[q];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 10; ++q) L.sq[5][q][lane] = rhs.v[q];
-                }
-                L.rflag[lane] = (okr ? 2u : 0u) | ((v & 1u) << 4);
-                COOP_T(6);
-            }
-        } else if (wave == 2) {
-            fe26 y, ny;
-            fe26_sqrt_cand(y, rhs);
-            fe26_sqr(t, y);
-            fe26_sub<3>(t, t, rhs);
-            okr = okr && fe26_is_zero(t);
-            fe26_normalize(y);
-            fe26_neg<2>(ny, y);
-            fe26_normalize(ny);
-            fe26_cmov(y, ny, (y.v[0] & 1u) != (v & 1u));
-            lds_store_fe26(L.ys, y, lane);
-            L.rflag[lane] = okr ? 2u : 0u;
-            COOP_T(6);
-        } else {
-            Aff26 R, A[8];
-            fe26_mul(R.x, rhs, X);  // w x
-            fe26_sqr(R.y, rhs);     // w^2
-            fe26 Zc, beta;
-            {
-                Jac26 T[8];
-                multiples8_26(T, R);
-                coz_table26(A, Zc, T);
-            }
-            fe26_const(beta, kGlvBeta);
-            Unroll<0, 8>::run([&](auto J) {
-                constexpr int j = decltype(J)::value;
-                fe26 bx;
-                fe26_mul(bx, A[j].x, beta);
-                if constexpr (TRIO) {
-                    lds_store_limbs26(L.tab[j], A[j].x, lane);
-                    lds_store_limbs26(L.tab[j] + 10, A[j].y, lane);
-                    lds_store_limbs26(L.tabphx[j], bx, lane);
-                } else {
-                    lds_store_fe26(L.tab[j], A[j].x, lane);
-                    lds_store_fe26(L.tab[j] + 8, A[j].y, lane);
-                    lds_store_fe26(L.tabphx[j], bx, lane);
-                }
-            });
-            lds_store_fe26(L.zc, Zc, lane);
+            coop26_table_to_lds<true>(L, P, lane);
             COOP_T(6);
         }
     }
-    if (!ok) {  // keep the scalar arithmetic well defined on rejected lanes
-        fe_zero(r);
-        r.v[0] = 1;
-        fe_zero(s);
-        if (kVer) s.v[0] = 1;
-    }
-    if (wave == 3) {
-        fe e;
-        fe_zero(e);
-        if (active) io.template digest<KECCAK256>(i, e);
-        reduce_once(e, ParamN1::M);
-        lds_store_fe(L.xe, e, lane);
-        coop_post(&L.post[1]);
-        COOP_T(7);
-    } else if (wave == 0) {
-        fe rm, rinv;  // verify: w = s^-1 in this slot
-        FieldN1::from_plain(rm, kVer ? s : r);
-        if constexpr (TRIO) FieldInv<FieldN1>::inv_pipe(rinv, rm);  // (pipelined: this kernel has the registers)
-        else FieldInv<FieldN1>::inv(rinv, rm);
-        lds_store_fe(L.xrinv, rinv, lane);
-        coop_post(&L.post[0]);
-        COOP_T(7);
-    }
-    if (kVer || kSplit || wave != 2) {
-        coop_wait(&L.post[0]);
-        coop_wait(&L.post[1]);
-        fe e, rinv, u1;
-        lds_load_fe(e, L.xe, lane);
-        lds_load_fe(rinv, L.xrinv, lane);
-        FieldN1::mul(u1, e, rinv);  // recover: u1 = -e / r; verify: u1 = e / s
-        if (!kVer) FieldN1::neg(u1, u1);
-        if (wave == 1) {
-            fe u2, k1, k2;
-            FieldN1::mul(u2, kVer ? r : s, rinv);  // recover: s / r; verify: r / s
-            bool neg1, neg2;
-            glv_split(k1, neg1, k2, neg2, u2);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                L.k[0][q][lane] = k1.v[q];
-                L.k[1][q][lane] = k2.v[q];
-            }
-            L.flags[lane] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
-            if constexpr (kSplit) coop_post(&L.spost[0]);  // phase C may start: the table, Zc, k and the flags
-        }
+    coop26_post_e_inv<true, true>(L, io, i, active, ok, r, s, wave, lane);
+    {
+        fe u1;
+        coop26_u1_glv<true>(u1, L, ok, r, s, wave, lane);
         Jac26 G;
-        // recover: wave 2 takes the square root, so the comb windows go to waves 0, 3 and 1; verify: wave 2
-        // joins (wave 3 also adds wave 0's partial, wave 1 builds the table first)
-        // with the split root wave 2 joins after the head, and no partial is added here: waves 0 / 3 / 2 / 1
-        // take windows [0, a) / [a, b) / [b, c) / [c, 16) of BCOSGPU_TRIO_SPLIT_WIN = a, b, c
-        const int slo = wave == 0 ? 0 : wave == 3 ? kSw[0] : wave == 2 ? kSw[1] : kSw[2];
-        const int shi = wave == 0 ? kSw[0] : wave == 3 ? kSw[1] : wave == 2 ? kSw[2] : 16;
-        if (kSplit && slo == shi) {
-            CurveK1x::set_inf(G);
-        } else if (tab_bits == kWideBits) {  // 16 windows of the 16-bit comb: 7 / 7 / 2; verify 6 / 4 / 5 / 1
-            const int lo = kSplit ? slo : kVer ? (wave == 0 ? 0 : wave == 3 ? 6 : wave == 2 ? 10 : 15) : (wave == 0 ? 0 : wave == 3 ? 7 : 14);
-            const int hi = kSplit ? shi : kVer ? (wave == 0 ? 6 : wave == 3 ? 10 : wave == 2 ? 15 : 16) : (wave == 0 ? 7 : wave == 3 ? 14 : 16);
-            comb_range26w<kWideBits>(G, u1, tab, lo, hi);
-        } else {  // 32 windows of the 8-bit comb: 12 / 12 / 8; verify 11 / 8 / 11 / 2
-            const int lo = kSplit ? 2 * slo : kVer ? (wave == 0 ? 0 : wave == 3 ? 11 : wave == 2 ? 19 : 30) : (wave == 0 ? 0 : wave == 3 ? 12 : 24);
-            const int hi = kSplit ? 2 * shi : kVer ? (wave == 0 ? 11 : wave == 3 ? 19 : wave == 2 ? 30 : 32) : (wave == 0 ? 12 : wave == 3 ? 24 : 32);
-            comb_range26w<8>(G, u1, tab, lo, hi);
-        }
-        // G0 + G3 on wave 3 while phase A waits for wave 1's last window (one addition off phase D)
-        if constexpr (kSplit) {
-            coop26_store_jac(L.pt[wave == 0 ? 3 : wave == 3 ? 4 : wave == 2 ? 0 : 2], G, lane);
-            coop_post(&L.spost[1 + wave]);
-        } else if (wave == 0) {
-            coop26_store_jac(L.pt[2], G, lane);
-            coop_post(&L.post[2]);
-        } else if (wave == 3) {
-            Jac26 G0, S;
-            coop_wait(&L.post[2]);
-            coop26_load_jac(G0, L.pt[2], lane);
-            CurveK1x::add(S, G0, G);
-            coop26_store_jac(L.pt[3], S, lane);
-        } else if (wave == 1) {
-            coop26_store_jac(L.pt[4], G, lane);
-        } else {  // verify: wave 2's windows
-            coop26_store_jac(L.pt[0], G, lane);
-        }
+        comb_share_range(G, u1, tab, tab_bits, kTrioVerifyShare, wave);
+        coop26_store_partial(L, G, wave, lane);
     }
     COOP_T(1);
-    // (the split root: each wave enters phase C once wave 1 has posted the table and the scalars; what the
-    // other waves leave in LDS is read in phase D only, behind their own flags or a barrier)
-    if constexpr (kSplit) coop_wait(&L.spost[0]);
-    else __syncthreads();
-    // ---------------------------------------------------------------- phase C: two cooperative GLV chains
-    if constexpr (TRIO) {
-        const TrioLane T(lane);
-        const int pos = lane & 15, trio_idx = pos / 3;
-        const int chain = wave & 1, tl = (wave >> 1) * 20 + (lane >> 4) * 5 + (trio_idx < 5 ? trio_idx : 4);
-        // (the split root: wave 2's rflag is read in phase D, behind a barrier)
-        const uint32_t tflags = kSplit ? L.flags[tl] : L.flags[tl] | L.rflag[tl];
-        TrioPt acc;
-        {
-            fe k;
-            fe_zero(k);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) k.v[q] = L.k[chain][q][tl];
-            const bool neg = chain == 0 ? (tflags & 4u) != 0 : (tflags & 8u) != 0;
-            const bool phi = chain == 1;
-            // digits 32 and 31 together (16 d32 + d31 = 2a + b): a R from the table, one doubling, b R
-            trio_chain_start(acc, k.v[3], [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
-            shl4_128(k);  // booth_digit128 goes on at digit 30
-#if BCOSGPU_TRIO_WINDOW
-            TrioAcc la;
-            trio_acc_from(la, acc);
-#pragma unroll 1
-            for (int w = 30; w >= 0; --w)
-                trio_window(la, booth_digit128(k), [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);
-            trio_acc_to(acc, la, T);
-#else
-#pragma unroll 1
-            for (int w = 30; w >= 0; --w) {
-                fe26 zz;
-#pragma unroll kTrioDblUnroll
-                for (int q = 0; q < 3; ++q) trio_dbl(acc, T);
-                trio_dbl_zz(acc, zz, T);  // + Z^2 for the addition
-                trio_add_digit_zz(acc, L, tl, booth_digit128(k), neg, phi, zz, T);
-            }
-#endif
-        }
-        COOP_T(2);
-        // ------------------------------------------------------------ phase D on the trios
-        // chain 0 (waves 0, 2) takes chain 1's point through LDS and adds it (E_w), maps to E (Z Zc y)
-        // and adds the G part, which chain 1 (waves 1, 3) sums meanwhile from phase A's two comb
-        // partials; all three additions are trio_add (6 product levels instead of 16 products on one
-        // lane).  Then the inversion and the affine map on lane 2 of each trio, the address Keccak on
-        // lane PAIRS (KeccakPair) of the chain-0 waves, and the outputs from lane 2.  The buffers reuse
-        // the table's LDS once every wave is past phase C (with the split root, whose chain-1 waves run
-        // ahead, they are Trio26Lds::xg instead, and its own schedule follows below).
-        uint32_t* const xbuf = kSplit ? &L.xg[wave >> 1][0][0] : &L.tab[0][0][0] + (wave >> 1) * kTrioWords * 64;
-        uint32_t* const gbuf =
-            kSplit ? &L.xg[2 + (wave >> 1)][0][0] : &L.tab[0][0][0] + (2 + (wave >> 1)) * kTrioWords * 64;
-        uint32_t* const mbuf = &L.tabphx[0][0][0];  // [40][16] pubkey messages, then [40][8] digests
-        const uint64_t ti = static_cast<uint64_t>(blockIdx.x) * TPW + tl;
-        const bool real = T.r2 && trio_idx < 5, tactive = ti < n;
-        fe26 zcy;
-        fe ax, ay;
-        bool ok2 = false;
-        if constexpr (!kSplit) __syncthreads();  // no wave reads the table any more
-        if constexpr (kSplit) {
-            // The split root's phase D.  The chains' sum S lies on E_w; with l = Zc y and K = l^2 = Zc^2 w it is
-            // the point (X K, Y K l, Z K) of E (trio_scale_xz, trio_scale_y), whose X and Z hold no y.  So the Z
-            // of the last addition T + S_E (T the G part) needs no y: chain 0 computes it alone (trio_add_z)
-            // and starts Z^-1, while chain 1 finishes the root, runs the complete addition and hands over
-            // X3, Y3.  Chain 1's waves leave phase A, and so phase C, before chain 0's: they sum the comb
-            // partials in that lead, behind flags instead of barriers.
-            constexpr bool kPairInv = BCOSGPU_TRIO_INV_SPLIT != 0 && kCut == 1;
-            const auto load_zc_w = [&](fe26& zc, fe26& w) {
-                lds_load_fe26(zc, L.zc, tl);
-#pragma unroll
-                for (int q = 0; q < 10; ++q) w.v[q] = L.sq[5][q][tl];
-                F26_SETM(w, 2);
-            };
-            TrioPt SE;
-            fe26 zi2, zi3;  // chain 0: Z^-2, Z^-3
-            fe26_zero(zi2);
-            fe26_zero(zi3);
-            if (chain == 1) {  // its chain's point to the partner; T = the sum of phase A's comb partials
-                trio_store(xbuf, acc, lane);
-                coop_post(&L.spost[5 + (wave >> 1)]);
-                coop_wait(&L.spost[1 + 0]);
-                coop_wait(&L.spost[1 + 3]);
-                if constexpr (kSw[1] < kSw[2]) coop_wait(&L.spost[1 + 2]);
-                if constexpr (kSw[2] < 16) coop_wait(&L.spost[1 + 1]);
-                Jac26 Ga, Gb;
-                TrioPt A, B;
-                coop26_load_jac(Ga, L.pt[3], tl);
-                coop26_load_jac(Gb, L.pt[4], tl);
-                trio_from_jac(A, Ga, T);
-                trio_from_jac(B, Gb, T);
-                trio_add(A, A, B, T);
-                if constexpr (kSw[1] < kSw[2]) {
-                    coop26_load_jac(Gb, L.pt[0], tl);
-                    trio_from_jac(B, Gb, T);
-                    trio_add(A, A, B, T);
-                }
-                if constexpr (kSw[2] < 16) {
-                    coop26_load_jac(Gb, L.pt[2], tl);
-                    trio_from_jac(B, Gb, T);
-                    trio_add(A, A, B, T);
-                }
-                trio_store(gbuf, A, lane);
-            } else {  // S = k1 R' + k2 phi(R') for the partner, and its X K, Z K here
-                TrioPt P1;
-                coop_wait(&L.spost[5 + (wave >> 1)]);
-                trio_load(P1, xbuf, lane);
-                trio_add(acc, acc, P1, T);
-                trio_store(xbuf, acc, lane);
-                fe26 zc, w, K;
-                coop_wait(&L.spost[1 + 2]);  // w is wave 2's (stored before its comb partial)
-                load_zc_w(zc, w);
-                fe26_sqr(K, zc);
-                fe26_mul(K, K, w);
-                trio_scale_xz(SE, acc, K, T);
-            }
-            __syncthreads();  // every wave is past phase C and phase A; S and T are in LDS
-            const uint32_t rfl = L.rflag[tl];
-            if (chain == 0) {
-                TrioPt G;
-                trio_load(G, gbuf, lane);
-                fe26 Z3;
-                trio_add_z(Z3, G, SE, T);
-                COOP_T(4);
-                fe z, zi;
-                fe26_to_fe(z, Z3);
-                if constexpr (kPairInv) {
-                    FieldK1::normalize(z);
-                    int32_t* const pq = reinterpret_cast<int32_t*>(&L.pt[0][0][0]);
-                    int32_t* const ring = pq + (wave >> 1) * (kInvRing * 4 * 64);
-                    int32_t* const dq = pq + 2 * kInvRing * 4 * 64 + (wave >> 1) * 9 * 64;
-                    const int32_t fs = modinv_pair_fg(z, kMod30K1P, ring, L.invq[wave >> 1], lane);
-                    modinv_pair_finish(zi, fs, kMod30K1P, dq, L.invq[wave >> 1], lane);
-                } else {
-                    FieldInv<FieldK1>::inv_pipe(zi, z);
-                }
-                COOP_T(5);
-                fe26 zi26;
-                fe26_from_fe(zi26, zi);
-                fe26_sqr(zi2, zi26);
-                fe26_mul(zi3, zi2, zi26);
-            } else {
-                TrioPt S, G;
-                trio_load(S, xbuf, lane);
-                trio_load(G, gbuf, lane);
-                fe26 y, ny, t, zc, w, K, l;
-                load_zc_w(zc, w);
-                fe26_sqr(K, zc);
-                fe26_mul(K, K, w);
-                trio_scale_xz(SE, S, K, T);  // (before the tail: less work between y and the hand-over)
-                {
-                    fe26 st[kLive];
-#pragma unroll
-                    for (int j = 0; j < kLive; ++j) {
-#pragma unroll
-                        for (int q = 0; q < 10; ++q) st[j].v[q] = L.sq[j][q][tl];
-                        F26_SETM(st[j], 1);
-                    }
-                    fe26_sqrt_tail<kCut>(y, st);
-                }
-                fe26_sqr(t, y);
-                fe26_sub<3>(t, t, w);
-                const bool on = fe26_is_zero(t);  // y^2 = w: r is the x of a curve point
-                fe26_normalize(y);
-                fe26_neg<2>(ny, y);
-                fe26_normalize(ny);
-                fe26_cmov(y, ny, (y.v[0] & 1u) != ((rfl >> 4) & 1u));
-                COOP_T(4);
-                fe26_mul(l, zc, y);
-                trio_scale_y(SE, l, T);
-                trio_add(S, G, SE, T);  // T first: S_E = T doubles T, which holds no y
-                trio_store(xbuf, S, lane);
-                if (real) L.yok[tl] = on ? 1u : 0u;
-                COOP_T(5);
-                if constexpr (kPairInv) {
-                    const int32_t* const pq = reinterpret_cast<const int32_t*>(&L.pt[0][0][0]);
-                    modinv_pair_de(kMod30K1P, pq + (wave >> 1) * (kInvRing * 4 * 64),
-                                   reinterpret_cast<int32_t*>(&L.pt[0][0][0]) + 2 * kInvRing * 4 * 64 + (wave >> 1) * 9 * 64,
-                                   L.invq[wave >> 1], lane);
-                }
-            }
-            __syncthreads();  // X3, Y3 and the verdicts are in LDS
-            if (chain == 0) {
-                TrioPt O;
-                trio_load(O, xbuf, lane);
-                ok2 = (tflags & 1u) != 0u && (rfl & 2u) != 0u && L.yok[tl] != 0u && !O.inf;
-                fe26 X, Y;  // lane 2 holds X3 (Xs), Y3 (S1)
-                fe26_mul(X, O.Xs, zi2);
-                fe26_mul(Y, O.S1, zi3);
-                fe26_to_fe(ax, X);
-                fe26_to_fe(ay, Y);
-                if (real) {
-                    uint32_t m[16];
-                    fe_to_be_words(m, ax);
-                    fe_to_be_words(m + 8, ay);
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) mbuf[16 * tl + q] = m[q];
-                }
-            }
-        } else {
-        if (chain == 1) {
-            trio_store(xbuf, acc, lane);
-        } else if constexpr (kVer) {
-            lds_load_fe26(zcy, L.zc, tl);  // the co-Z table of P itself: Z Zc
-        } else {
-            fe26 zc, y;
-            lds_load_fe26(zc, L.zc, tl);
-            lds_load_fe26(y, L.ys, tl);
-            fe26_mul(zcy, zc, y);
-        }
-        __syncthreads();
-        if (chain == 1) {  // G = (G0 + G3) + G1 (+ G2, verify) (phase A's partials)
-            Jac26 Ga, Gb;
-            TrioPt A, B;
-            coop26_load_jac(Ga, L.pt[3], tl);
-            coop26_load_jac(Gb, L.pt[4], tl);
-            trio_from_jac(A, Ga, T);
-            trio_from_jac(B, Gb, T);
-            trio_add(A, A, B, T);
-            if constexpr (kVer) {
-                coop26_load_jac(Gb, L.pt[0], tl);
-                trio_from_jac(B, Gb, T);
-                trio_add(A, A, B, T);
-            }
-            trio_store(gbuf, A, lane);
-        } else {  // R = (k1 R' + k2 phi(R')) on E_w, then (X, Y, Z Zc y) on E
-            TrioPt P1;
-            trio_load(P1, xbuf, lane);
-            trio_add(acc, acc, P1, T);
-            fe26_mul(acc.Zs, acc.Zs, zcy);
-        }
-        __syncthreads();
-        if (chain == 0 && kVer) {
-            TrioPt G;
-            trio_load(G, gbuf, lane);
-            trio_add(acc, acc, G, T);
-            // x(Q) = X / Z^2 must be r or r + n (when r + n < p): X == c Z^2, projectively, on lane 2
-            fe rr, r2, xw, cw;
-            lds_load_fe(rr, L.ys, tl);
-            fe26 z2, c, rhs;
-            fe26_sqr(z2, acc.Zs);
-            fe26_from_fe(c, rr);
-            fe26_mul(rhs, c, z2);
-            fe26_to_fe(xw, acc.Xs);
-            fe26_to_fe(cw, rhs);
-            bool match = fe_eq_raw(xw, cw);
-            const uint32_t carry = fe_add_k(r2, rr, ParamN1::M);
-            const bool second = carry == 0u && fe_lt_k(r2, FieldK1::P);
-            fe26_from_fe(c, second ? r2 : rr);
-            fe26_mul(rhs, c, z2);
-            fe26_to_fe(cw, rhs);
-            match = match || (second && fe_eq_raw(xw, cw));
-            ok2 = (tflags & 3u) == 3u && !acc.inf && match;
-        } else if (chain == 0) {
-            TrioPt G;
-            trio_load(G, gbuf, lane);
-            trio_add(acc, acc, G, T);
-            ok2 = (tflags & 3u) == 3u && !acc.inf;
-            COOP_T(4);
-            fe z, zi;
-            fe26_to_fe(z, acc.Zs);
-#if BCOSGPU_TRIO_INV_SPLIT
-            // Z^-1 over the wave pair: the divsteps and (f, g) here, the (d, e) updates on the chain-1
-            // partner (same txs, same lanes), through a ring in the chain points' LDS (free after the
-            // barrier above): modinv_pair_*
-            FieldK1::normalize(z);
-            int32_t* const pq = reinterpret_cast<int32_t*>(&L.pt[0][0][0]);
-            int32_t* const ring = pq + (wave >> 1) * (kInvRing * 4 * 64);
-            int32_t* const dq = pq + 2 * kInvRing * 4 * 64 + (wave >> 1) * 9 * 64;
-            const int32_t fs = modinv_pair_fg(z, kMod30K1P, ring, L.invq[wave >> 1], lane);
-            modinv_pair_finish(zi, fs, kMod30K1P, dq, L.invq[wave >> 1], lane);
-#else
-            FieldInv<FieldK1>::inv_pipe(zi, z);
-#endif
-            COOP_T(5);
-            fe26 zi26, zi2, zi3, X, Y;  // lane 2 holds X (Xs), Y (S1), Z
-            fe26_from_fe(zi26, zi);
-            fe26_sqr(zi2, zi26);
-            fe26_mul(X, acc.Xs, zi2);
-            fe26_mul(zi3, zi2, zi26);
-            fe26_mul(Y, acc.S1, zi3);
-            fe26_to_fe(ax, X);
-            fe26_to_fe(ay, Y);
-            if (real) {
-                uint32_t m[16];
-                fe_to_be_words(m, ax);
-                fe_to_be_words(m + 8, ay);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) mbuf[16 * tl + q] = m[q];
-            }
-        }
-#if BCOSGPU_TRIO_INV_SPLIT
-        else if (!kVer) {  // chain 1: the (d, e) half of the partner's Z^-1
-            const int32_t* const pq = reinterpret_cast<const int32_t*>(&L.pt[0][0][0]);
-            modinv_pair_de(kMod30K1P, pq + (wave >> 1) * (kInvRing * 4 * 64),
-                           reinterpret_cast<int32_t*>(&L.pt[0][0][0]) + 2 * kInvRing * 4 * 64 + (wave >> 1) * 9 * 64,
-                           L.invq[wave >> 1], lane);
-        }
-#endif
-        }  // !kSplit
-        __syncthreads();
-        if (chain == 0 && io.want_addr()) {  // Keccak256(x || y) on lane pairs: tx j = lane / 2 of the wave
-            const KeccakPair kp;
-            const int j = lane >> 1, t = (wave >> 1) * 20 + (j < 20 ? j : 0);
-            uint32_t d[4];
-            kp.hash(reinterpret_cast<const uint8_t*>(mbuf + 16 * t), 64u, d);
-            if (j < 20) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) mbuf[640 + 8 * t + 2 * q + (lane & 1)] = d[q];
-            }
-        }
-        __syncthreads();
-        if (chain == 0 && real && tactive) {
-            uint32_t ad[5] = {0, 0, 0, 0, 0};
-            if (ok2 && io.want_addr()) {
-#pragma unroll
-                for (int q = 0; q < 5; ++q) ad[q] = mbuf[640 + 8 * tl + 3 + q];  // right160
-            }
-            io.finish(ti, ok2, ad, &ax, &ay);
-        }
-        COOP_T(3);
+    __syncthreads();
+    // ---------------------------------------------------------------- phase C: one GLV chain per trio
+    const TrioLane T(lane);
+    const TrioSeat seat(wave, lane, T);
+    const int chain = seat.chain, tl = seat.tl;
+    const uint32_t tflags = L.flags[tl] | L.rflag[tl];
+    TrioPt acc;
+    trio_glv_chain(acc, L, chain, tl, tflags, T);
+    COOP_T(2);
+    // ---------------------------------------------------------------- phase D on the trios
+    uint32_t* const xbuf = &L.tab[0][0][0] + (wave >> 1) * kTrioWords * 64;
+    uint32_t* const gbuf = &L.tab[0][0][0] + (2 + (wave >> 1)) * kTrioWords * 64;
+    const uint64_t ti = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + tl;
+    fe26 zcy;
+    bool ok2 = false;
+    __syncthreads();  // no wave reads the table any more
+    if (chain == 1) trio_store(xbuf, acc, lane);
+    else lds_load_fe26(zcy, L.zc, tl);  // the co-Z table of P itself: Z Zc
+    __syncthreads();
+    if (chain == 1) {  // G = (G0 + G3) + G1 + G2 (phase A's partials)
+        TrioPt A;
+        trio_sum_partials<true, false>(A, L, tl, T);
+        trio_store(gbuf, A, lane);
+    } else {  // k1 P' + k2 phi(P') on the table's curve, then (X, Y, Z Zc) on E
+        TrioPt P1;
+        trio_load(P1, xbuf, lane);
+        trio_add(acc, acc, P1, T);
+        fe26_mul(acc.Zs, acc.Zs, zcy);
     }
-    if constexpr (!TRIO) {
-        const uint32_t flags = L.flags[lane] | L.rflag[lane];
-        {
-            Coop26Ctx c{&L, wave >> 1, wave & 1, lane, false};
-            fe k;
-            fe_zero(k);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) k.v[q] = L.k[c.chain][q][lane];
-            const bool neg = c.chain == 0 ? (flags & 4u) != 0 : (flags & 8u) != 0;
-            const bool phi = c.chain == 1;
-            Jac26 acc;
-            CurveK1x::set_inf(acc);
-            coop26_add_digit(acc, c, static_cast<int>(k.v[3] >> 31), neg, phi);  // digit 32 = bit 127
-#pragma unroll 1
-            for (int w = 31; w >= 0; --w) {
-                coop26_dbl<0>(acc, c);
-#ifdef BCOSGPU_COOP_TIMING
-                c.probe = blockIdx.x == 0 && w == 20;
-#endif
-                coop26_dbl<3>(acc, c);
-#ifdef BCOSGPU_COOP_TIMING
-                c.probe = false;
-                if (blockIdx.x == 0 && w == 20 && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][5] = clock64();
-#endif
-                coop26_dbl<0>(acc, c);
-                coop26_dbl<3>(acc, c);
-#ifdef BCOSGPU_COOP_TIMING
-                if (blockIdx.x == 0 && w == 20 && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][6] = clock64();
-#endif
-                coop26_add_digit(acc, c, booth_digit128(k), neg, phi);
-#ifdef BCOSGPU_COOP_TIMING
-                if (blockIdx.x == 0 && w == 20 && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][7] = clock64();
-#endif
-            }
-            COOP_T(2);
-            if (c.role == 0) coop26_store_jac(L.pt[c.chain], acc, lane);
-        }
-        __syncthreads();
-        // ---------------------------------------------------------------- phase D (on fe26 as well)
-        if (wave == 1) {  // G part: (partials 0 + 1, phase A) + 2
-            Jac26 G01, G2, U;
-            coop26_load_jac(G01, L.pt[3], lane);
-            coop26_load_jac(G2, L.pt[4], lane);
-            CurveK1x::add(U, G01, G2);
-            coop26_store_jac(L.pt[2], U, lane);
-        } else if (wave == 0) {  // R part: co-Z curve -> E_w (Z * Zc) -> E (Z * y)
-            Jac26 P0, P1, Q;
-            coop26_load_jac(P0, L.pt[0], lane);
-            coop26_load_jac(P1, L.pt[1], lane);
-            fe26 Zc, y;
-            lds_load_fe26(Zc, L.zc, lane);
-            lds_load_fe26(y, L.ys, lane);
-            CurveK1x::add(Q, P0, P1);
-            fe26_mul(Zc, Zc, y);
-            fe26_mul(Q.Z, Q.Z, Zc);
-            coop26_store_jac(L.pt[0], Q, lane);
-        }
-        __syncthreads();
-        if (wave == 0 && active) {
-            Jac26 Q, G, R;
-            coop26_load_jac(Q, L.pt[0], lane);
-            coop26_load_jac(G, L.pt[2], lane);
-            CurveK1x::add(R, Q, G);
-            const bool ok2 = (flags & 3u) == 3u && !R.inf;
-            COOP_T(4);
-            fe z, zi, ax, ay;
-            fe26_to_fe(z, R.Z);
-            FieldInv<FieldK1>::inv(zi, z);
-            COOP_T(5);
-            fe26 zi26, zi2, zi3, X, Y;
-            fe26_from_fe(zi26, zi);
-            fe26_sqr(zi2, zi26);
-            fe26_mul(X, R.X, zi2);
-            fe26_mul(zi3, zi2, zi26);
-            fe26_mul(Y, R.Y, zi3);
-            fe26_to_fe(ax, X);
-            fe26_to_fe(ay, Y);
-            uint32_t ad[5] = {0, 0, 0, 0, 0};
-            if (ok2 && io.want_addr()) keccak_address(ad, ax, ay);
-            io.finish(i, ok2, ad, &ax, &ay);
-        }
-        COOP_T(3);
+    __syncthreads();
+    if (chain == 0) {
+        TrioPt G;
+        trio_load(G, gbuf, lane);
+        trio_add(acc, acc, G, T);
+        // x(Q) = X / Z^2 must be r or r + n (when r + n < p): X == c Z^2, projectively, on lane 2
+        fe rr, r2, xw, cw;
+        lds_load_fe(rr, L.ys, tl);
+        fe26 z2, c, rhs;
+        fe26_sqr(z2, acc.Zs);
+        fe26_from_fe(c, rr);
+        fe26_mul(rhs, c, z2);
+        fe26_to_fe(xw, acc.Xs);
+        fe26_to_fe(cw, rhs);
+        bool match = fe_eq_raw(xw, cw);
+        const uint32_t carry = fe_add_k(r2, rr, ParamN1::M);
+        const bool second = carry == 0u && fe_lt_k(r2, FieldK1::P);
+        fe26_from_fe(c, second ? r2 : rr);
+        fe26_mul(rhs, c, z2);
+        fe26_to_fe(cw, rhs);
+        match = match || (second && fe_eq_raw(xw, cw));
+        ok2 = (tflags & 3u) == 3u && !acc.inf && match;
     }
+    // (the two barriers of the recovery kernel's tail, which this kernel's schedule has carried since the
+    // two shared a body; it hashes nothing between them)
+    __syncthreads();
+    __syncthreads();
+    if (chain == 0 && seat.real && ti < n) {
+        const uint32_t ad[5] = {0, 0, 0, 0, 0};
+        io.finish(ti, ok2, ad, nullptr, nullptr);
+    }
+    COOP_T(3);
 }
 
 template <class IO>
 __global__ __launch_bounds__(256, 1) void tx_verify_coop26_kernel(IO io, uint64_t n, const uint32_t* __restrict__ tab) {
-    coop26_body<false, kRecover>(io, n, tab, 8);
+    coop26_body(io, n, tab);
 }
 
-// The trio kernel: phase C's doublings and mixed additions cost one multiplication of latency per
-// dependency level (3 per doubling, 5 per addition) with DPP exchanges inside a wave instead of LDS
-// exchanges and barriers between waves, and 40 txs per workgroup spread a 10k batch over 250 CUs
-// instead of 157.  Bit-identical to tx_verify_kernel<0, *>.
+// Bit-identical to tx_verify_kernel<0, *>.
 template <class IO>
 __global__ __launch_bounds__(256, 1) void tx_verify_trio26_kernel(IO io, uint64_t n, const uint32_t* __restrict__ tab,
                                                                   int tab_bits) {
-    coop26_body<true, kRecover>(io, n, tab, tab_bits);
+    trio26_recover_body(io, n, tab, tab_bits);
 }
 
 // SignatureCrypto::verify(pub, hash, sig) with a known key on lane trios (KeyIO): the sealer-signature
@@ -1808,7 +1864,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_trio26_kernel(IO io, uint64_
 // sig_verify_kernel<secp256k1, *> (secp256k1_verify_lane).
 __global__ __launch_bounds__(256, 1) void sig_verify_trio26_kernel(KeyIO io, uint64_t n, const uint32_t* __restrict__ tab,
                                                                    int tab_bits) {
-    coop26_body<true, kVerify>(io, n, tab, tab_bits);
+    trio26_verify_body(io, n, tab, tab_bits);
 }
 
 int launch_sig_verify_small_secp(const KeyIO& io, uint64_t n, hipStream_t st) {

@@ -19,6 +19,14 @@
 #include <string>
 #include <vector>
 
+namespace bcosgpu {
+// ecc_pair.hip's launcher names the row kernel's (ecc_row.hip), which this probe neither builds nor runs
+template <class IO>
+int launch_sm2_verify_row(const IO&, uint64_t, hipStream_t) {
+    return BCOSGPU_E_ARG;
+}
+}  // namespace bcosgpu
+
 int main(int argc, char** argv) {
     const int reps = argc > 1 ? atoi(argv[1]) : 4;
     // low Booth windows on waves 2 and 3 (sm2_low_chain): argv[3], else the library's default

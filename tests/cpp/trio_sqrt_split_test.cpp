@@ -1,5 +1,5 @@
 // trio_sqrt_split_test.cpp -- host build (FE26_CHECK) of the two pieces of the lane-trio kernel's split
-// square root (ecc_coop.hip, BCOSGPU_TRIO_SQRT_SPLIT):
+// square root (ecc_coop.hip, trio26_recover_body):
 //  (a) fe26_sqrt_head<CUT> then fe26_sqrt_tail<CUT> against fe26_sqrt_cand, limb for limb, for both cuts:
 //      random elements, 0, 1, quadratic non-residues, magnitude-2 inputs (random and bound-hugging limbs);
 //  (b) the split last addition: chain 0's Z3 (trio_scale_xz, trio_add_z) together with the

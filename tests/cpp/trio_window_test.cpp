@@ -193,7 +193,7 @@ int booth_digit(u128& k) {
     return static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
 }
 
-// the window that the lean one replaces (ecc_coop.hip with BCOSGPU_TRIO_WINDOW = 0)
+// the window that the lean one replaced (trio_dbl x 3, trio_dbl_zz, trio_madd_zz: removed from ecc_coop.hip)
 void old_window(TrioPt& acc, const Table& Tb, int d, bool neg, bool phi, const TrioLane& T) {
     fe26 zz;
     for (int q = 0; q < 3; ++q) trio_dbl(acc, T);

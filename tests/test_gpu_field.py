@@ -84,7 +84,7 @@ def test_montgomery_fields_and_inversions_vs_python():
     """FieldP2 (redc_sm2p), FieldN1 and FieldN2 with their mod_add_asm / mod_sub_asm, both Fermat chains of
     Mont<>::inv, FieldP2::inv, and the safegcd inversions (plain, pipelined, variable-time, and behind
     mont_inv_safegcd) with each modulus' ModInfo30, through fetest's field selector; cases and checker are
-    tests/mont_vectors.py.  The lane-split inversions (modinv_var_split_*, modinv_pair_*, inv_fg_rows) need
+    tests/mont_vectors.py.  The lane-split inversions (modinv_var_split_*, inv_fg_rows) need
     their kernels' LDS queues and stay covered end to end."""
     import mont_vectors as mv
     assert os.path.exists(EXE), "build fisco-bcos_amd/lib/fetest first (make -C fisco-bcos_amd)"

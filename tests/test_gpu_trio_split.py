@@ -1,5 +1,5 @@
 """The lane-trio recovery kernel (csrc/ecc_coop.hip, tx_verify_trio26_kernel) with the square root split
-between phase A and phase D (BCOSGPU_TRIO_SQRT_SPLIT): forced with bcosgpu_set_tx_kernel_policy(1, 1, 2, 1)
+between phase A and phase D (trio26_recover_body): forced with bcosgpu_set_tx_kernel_policy(1, 1, 2, 1)
 at 1, 39, 40, 41 and 81 signatures -- one partial workgroup, one short of a full one, a full one (40 txs: the
 20 / 21 boundary of its two wave pairs lies inside), one more than a workgroup, one more than two -- against
 the oracle as test_gpu_row._check does.  The inputs are signed by the oracle, so every case's accepted and
