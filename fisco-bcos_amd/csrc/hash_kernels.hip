@@ -13,10 +13,12 @@
 #include <mutex>
 #include <utility>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "hash_device.h"
 #include "sm3_x.h"
 #include "engine.h"
+#include "merkle_plan.h"
 
 namespace bcosgpu {
 
@@ -100,16 +102,28 @@ int launch_hash_batch(int hasher, const uint8_t* d_data, const uint64_t* d_off, 
     return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
 }
 
+// (hasher, width, x) -> the kernels' compile-time <H, W, X>: calls f(h, w, xc) with integral constants (usable as
+// template arguments), h = SM3 or KECCAK256 (any other hasher value), w = 2, 16 or 0 (the runtime width), xc = x
+// for SM3 and false for Keccak (X: the expanded-block SM3 variants; launches of kernels without it pass false)
+static_assert(KECCAK256 == kPlanKeccak256 && SM3 == kPlanSm3, "merkle_plan.h's hasher values");
+template <class F>
+static void with_hw(int hasher, int width, bool x, F&& f) {
+    const auto with_w = [&](auto h, auto xc) {
+        if (width == 2) f(h, std::integral_constant<int, 2>{}, xc);
+        else if (width == 16) f(h, std::integral_constant<int, 16>{}, xc);
+        else f(h, std::integral_constant<int, 0>{}, xc);
+    };
+    if (hasher != SM3) with_w(std::integral_constant<int, KECCAK256>{}, std::false_type{});
+    else if (x) with_w(std::integral_constant<int, SM3>{}, std::true_type{});
+    else with_w(std::integral_constant<int, SM3>{}, std::false_type{});
+}
+
 static void launch_level(int hasher, int width, const uint8_t* in, uint64_t nin, uint8_t* out,
                          uint64_t nout, hipStream_t st) {
     dim3 g(grid_for(nout, 256)), b(256);
-#define LVL(HH, WW) hipLaunchKernelGGL((merkle_level_kernel<HH, WW>), g, b, 0, st, in, nin, width, out, nout)
-    if (hasher == SM3) {
-        if (width == 2) LVL(SM3, 2); else if (width == 16) LVL(SM3, 16); else LVL(SM3, 0);
-    } else {
-        if (width == 2) LVL(KECCAK256, 2); else if (width == 16) LVL(KECCAK256, 16); else LVL(KECCAK256, 0);
-    }
-#undef LVL
+    with_hw(hasher, width, false, [&](auto h, auto w, auto) {
+        hipLaunchKernelGGL((merkle_level_kernel<h, w>), g, b, 0, st, in, nin, width, out, nout);
+    });
 }
 
 uint64_t merkle_size(uint64_t n, int width) {
@@ -128,12 +142,6 @@ uint64_t merkle_size(uint64_t n, int width) {
 // then every level whose groups lie inside it, through LDS, writing each node into the reference's
 // output vector as it goes (groups align with workgroups because B is a power of width); a single
 // 1024-thread workgroup then finishes the top levels.  Same output vector as the per-level path.
-struct TreeLevels {
-    uint64_t pos[64];  // tree entry of the count record of level l + 1 (level 0 = leaves)
-    uint64_t cnt[64];  // nodes of level l + 1
-    int nlev;          // levels above the leaves (the last has one node)
-};
-
 template <int H>
 __device__ __forceinline__ void hash_nodes(const uint8_t* src, uint32_t cnt, uint32_t d[8]) {
     const uint32_t len = cnt * 32u;
@@ -421,12 +429,6 @@ __global__ __launch_bounds__(1024) void merkle_top_kernel(int w, int l0, uint8_t
 // checks the emitted order on every build (tools/hazard_check.py fused_publish_order).  An acq_rel
 // counter (the language-level form) costs a buffer_wbl2 / buffer_inv of the XCD's L2 per hand-off:
 // 0.175 vs 0.130 ms per 100k-leaf width-2 Keccak root (profiles/r04_merkle_fused_order_ab.log).
-struct FusedTree {
-    TreeLevels t;
-    uint32_t ctr_off[64];  // first counter of level l (levels a + 1 .. nlev - 1)
-    int a;                 // levels above level 1 computed inside a wave (S = width^a)
-    uint32_t S;
-};
 
 __device__ __forceinline__ void st_dev(uint8_t* p, uint32_t v) {
     __hip_atomic_store(reinterpret_cast<uint32_t*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -571,7 +573,7 @@ __global__ __launch_bounds__(64) void merkle_fused_kernel(const uint8_t* __restr
 //    allocate): it takes the multi-launch path.
 //  - Pools of kFusedSlots slots are added on demand up to kFusedPools per device; past that the
 //    multi-launch path runs (bit-identical, slower at latency sizes) and a line on stderr says so once.
-static constexpr uint32_t kFusedCounters = 16384, kFusedSlots = 64, kFusedPools = 16;
+static constexpr uint32_t kFusedSlots = 64, kFusedPools = 16;  // (kFusedCounters: merkle_plan.h)
 namespace {
 struct SlotOwner {
     int device;
@@ -706,40 +708,6 @@ static uint32_t* fused_counter_slot(hipStream_t st) {
     return slot;
 }
 
-static constexpr uint64_t kFusedMaxWaves = 2048;  // level-1 waves (two per SIMD) up to which the one-launch path runs
-
-// the latency path; returns 1 when it does not apply (too wide a tree, no counter slot)
-static int launch_merkle_fused(int hasher, int width, const uint8_t* d_leaves, uint64_t n, uint8_t* d_tree,
-                               uint8_t* d_root, const TreeLevels& t, bool force, hipStream_t st) {
-    FusedTree f{};
-    f.t = t;
-    // S = width^a: Keccak level 0 on lane pairs (S <= 32), SM3 one lane per node (S <= 64)
-    const uint32_t cap = hasher == KECCAK256 ? 32u : 64u;
-    f.S = 1;
-    f.a = 0;
-    while (f.S * static_cast<uint32_t>(width) <= cap) {
-        f.S *= width;
-        ++f.a;
-    }
-    uint32_t off = 0;
-    for (int l = 0; l < t.nlev; ++l) {
-        f.ctr_off[l] = off;
-        if (l > f.a) off += static_cast<uint32_t>(t.cnt[l]);
-    }
-    if (off > kFusedCounters || (!force && (t.cnt[0] + f.S - 1) / f.S > kFusedMaxWaves)) return 1;
-    uint32_t* ctr = fused_counter_slot(st);
-    if (!ctr) return 1;
-    const dim3 g(static_cast<unsigned>((t.cnt[0] + f.S - 1) / f.S)), b(64);
-#define FUSED(HH, WW) hipLaunchKernelGGL((merkle_fused_kernel<HH, WW>), g, b, 0, st, d_leaves, n, width, d_tree, f, d_root, ctr)
-    if (hasher == SM3) {
-        if (width == 2) FUSED(SM3, 2); else if (width == 16) FUSED(SM3, 16); else FUSED(SM3, 0);
-    } else {
-        if (width == 2) FUSED(KECCAK256, 2); else if (width == 16) FUSED(KECCAK256, 16); else FUSED(KECCAK256, 0);
-    }
-#undef FUSED
-    return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
-}
-
 // ------------------------------------------------------------------ one launch, four-wave workgroups
 // The one-launch path for narrow Keccak trees (the production width 2, Merkle.h:36 / BlockImpl.h:125).
 // With one wave per workgroup (above) a width-2 tree needs 32 level-1 nodes per wave on lane pairs, i.e.
@@ -752,16 +720,6 @@ static int launch_merkle_fused(int hasher, int width, const uint8_t* d_leaves, u
 // with its eight 25-lane groups (width 2: 16 nodes -> 8 -> 4 -> 2 -> 1, one hand-off per four levels).
 // The hand-off is merkle_fused_kernel's: sc1 node stores, s_waitcnt vmcnt(0) + barrier before the counter
 // RMW, sc1 loads after it, compiler barriers at both points (tools/hazard_check.py checks the order).
-struct ClimbTree {
-    TreeLevels t;
-    uint32_t ctr_off[64];  // first arrival counter of level l (the top level of a climb step)
-    int kin;               // levels above level 1 inside a workgroup (B = width^kin)
-    int B;
-    int g;                 // levels per climb step: width^(g - 1) <= 8 first-level nodes (SM3: <= 64)
-    uint32_t coop_max;     // in-workgroup levels of at most this many nodes run on 25-lane groups
-    uint32_t pair_max;     // ... of at most this many (and more than coop_max) on lane pairs, else one lane
-    int pair;
-};
 
 // X (SM3, latency-sized trees of width > 2): the in-workgroup levels above level 1 and the climb steps'
 // levels expand their blocks in parallel first (sm3_level_x, as merkle_wg_kernel's X variant), so C1's SM3
@@ -885,253 +843,96 @@ __global__ __launch_bounds__(256) void merkle_subtree_kernel(const uint8_t* __re
     }
 }
 
-static constexpr uint64_t kClimbMaxWgs = 4096;  // level-1 workgroups up to which the four-wave path runs
-static constexpr int kClimbMaxWidth = 4;  // widths the four-wave path takes at latency sizes (wider: the one-wave one)
+// ------------------------------------------------------------------ the root launchers
+// plan_merkle (merkle_plan.h) says which paths to try and with what geometry; each launcher below launches its
+// part of the plan.  A one-launch path returns 1 when the stream gets no counter slot (a stream under capture,
+// every slot owned), and launch_merkle moves on to the plan's next path.
+struct MerkleArgs {  // launch_merkle's
+    int hasher, width;
+    const uint8_t* leaves;
+    uint64_t n;
+    uint8_t *tree, *root;
+    hipStream_t st;
+};
 
-// returns 1 when it does not apply (too many counters or workgroups, no counter slot)
-static int launch_merkle_climb(int hasher, int width, const uint8_t* d_leaves, uint64_t n, uint8_t* d_tree,
-                               uint8_t* d_root, const TreeLevels& t0, hipStream_t st, bool sm3x = false) {
-    ClimbTree f{};
-    f.B = 1;
-    f.kin = 0;
-    while (f.B * width <= 256) {
-        f.B *= width;
-        ++f.kin;
-    }
-    // more workgroups than CUs: the subtree kernel first for levels 0..k (width^k <= 64 level-0 nodes per
-    // thread), so that the climb kernel starts with one workgroup per CU
-    const uint64_t cus = static_cast<uint64_t>(cu_count());
-    // A/B hooks (read once): BCOSGPU_MERKLE_NOSUB=1 never runs the subtree kernel first (the climb kernel
-    // takes the leaves itself, two workgroups on some CUs); BCOSGPU_MERKLE_LATSCHED=1 keeps the latency
-    // schedule (25-lane groups from eight nodes down) even with more workgroups than CUs
-    static const bool nosub_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_NOSUB");
-        return e && e[0] == '1';
-    }();
-    static const bool latsched_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_LATSCHED");
-        return e && e[0] == '1';
-    }();
-    int k = -1;
-    if (!nosub_env && (t0.cnt[0] + f.B - 1) / f.B > cus) {
-        uint64_t span = 1;
-        for (int q = 0; q + 2 < t0.nlev && span <= 64; ++q, span *= width)
-            if ((t0.cnt[q + 1] + f.B - 1) / f.B <= cus) {
-                k = q;
-                break;
-            }
-    }
-    TreeLevels t = t0;  // the climb kernel's levels: those above level k, whose nodes are its leaves
-    if (k >= 0) {
-        t.nlev = t0.nlev - (k + 1);
-        for (int l = 0; l < t.nlev; ++l) {
-            t.pos[l] = t0.pos[l + k + 1];
-            t.cnt[l] = t0.cnt[l + k + 1];
-        }
-    }
-    f.t = t;
-    // width^(g - 1) <= 8 (SM3: 64) first-level nodes per step, and the step's width^g gathered children
-    // fit one LDS half (lds[0], 256 nodes): the step's first level writes lds[1] while reading them
-    f.g = 1;
-    for (int q = width; q <= (hasher == KECCAK256 ? 8 : 64) && q * width <= 256; q *= width) ++f.g;
-    const uint64_t wgs = (t.cnt[0] + f.B - 1) / f.B;
-    if (wgs > kClimbMaxWgs) return 1;
-    // one workgroup per CU: the latency schedule (25-lane groups from eight nodes down, lane pairs above,
-    // one lane per node only for level 1's 256); more: every SIMD runs several waves, so each level takes
-    // the fewest wave-cycles -- one lane per node (a wave pass of 64 nodes: 22k cycles) down to 64 nodes,
-    // lane pairs (32 nodes: 15k) down to 4, 25-lane groups (2 nodes: 9.4k) below
-    const bool latency = wgs <= static_cast<uint64_t>(cu_count()) || latsched_env;
-    f.coop_max = latency ? 8u : 2u;
-    f.pair_max = latency ? 128u : 32u;
-    f.pair = 1;
-    uint32_t off = 0;
-    for (int l = 0; l < t.nlev; ++l) {
-        f.ctr_off[l] = off;
-        if (l > f.kin) off += static_cast<uint32_t>(t.cnt[l]);
-    }
-    if (off > kFusedCounters) return 1;
-    uint32_t* ctr = fused_counter_slot(st);
+static int launch_merkle_fused(const MerkleArgs& a, const MerklePlan::Fused& p) {
+    uint32_t* ctr = fused_counter_slot(a.st);
     if (!ctr) return 1;
-    if (k >= 0) {
-        const dim3 gs(grid_for(t0.cnt[k], 256)), bs(256);
-#define SUB(HH, WW) hipLaunchKernelGGL((merkle_subtree_kernel<HH, WW>), gs, bs, 0, st, d_leaves, n, width, d_tree, t0, k)
-        if (hasher == SM3) {
-            if (width == 2) SUB(SM3, 2); else if (width == 16) SUB(SM3, 16); else SUB(SM3, 0);
-        } else {
-            if (width == 2) SUB(KECCAK256, 2); else if (width == 16) SUB(KECCAK256, 16); else SUB(KECCAK256, 0);
-        }
-#undef SUB
-        d_leaves = d_tree + 32ull * (t0.pos[k] + 1);
-        n = t0.cnt[k];
-    }
-    const dim3 g(static_cast<unsigned>(wgs)), b(256);
-#define CLIMB(HH, WW) hipLaunchKernelGGL((merkle_climb_kernel<HH, WW>), g, b, 0, st, d_leaves, n, width, d_tree, f, d_root, ctr)
-#define CLIMBX(HH, WW) hipLaunchKernelGGL((merkle_climb_kernel<HH, WW, true>), g, b, 0, st, d_leaves, n, width, d_tree, f, d_root, ctr)
-    if (hasher == SM3 && sm3x && width > 2 && latency) {
-        if (width == 16) CLIMBX(SM3, 16); else CLIMBX(SM3, 0);
-    } else if (hasher == SM3) {
-        if (width == 2) CLIMB(SM3, 2); else if (width == 16) CLIMB(SM3, 16); else CLIMB(SM3, 0);
-    } else {
-        if (width == 2) CLIMB(KECCAK256, 2); else if (width == 16) CLIMB(KECCAK256, 16); else CLIMB(KECCAK256, 0);
-    }
-#undef CLIMB
-#undef CLIMBX
-    return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
+    with_hw(a.hasher, a.width, false, [&](auto h, auto w, auto) {
+        hipLaunchKernelGGL((merkle_fused_kernel<h, w>), dim3(p.grid), dim3(64), 0, a.st, a.leaves, a.n, a.width, a.tree,
+                           p.f, a.root, ctr);
+    });
+    return 0;
 }
 
-static constexpr uint64_t kTopKernelMaxIn = 16384;  // inputs per level the single-workgroup kernel takes
-static constexpr uint64_t kPairMaxNodes = 32768;    // level-1 nodes up to which Keccak levels use lane pairs
+static int launch_merkle_climb(const MerkleArgs& a, const TreeLevels& t0, const MerklePlan::Climb& p) {
+    uint32_t* ctr = fused_counter_slot(a.st);
+    if (!ctr) return 1;
+    const uint8_t* leaves = a.leaves;
+    uint64_t n = a.n;
+    if (p.k >= 0) {  // levels 0 .. k first: level k's nodes are the climb kernel's leaves
+        with_hw(a.hasher, a.width, false, [&](auto h, auto w, auto) {
+            hipLaunchKernelGGL((merkle_subtree_kernel<h, w>), dim3(p.sub_grid), dim3(256), 0, a.st, leaves, n, a.width,
+                               a.tree, t0, p.k);
+        });
+        leaves = a.tree + 32ull * (t0.pos[p.k] + 1);
+        n = t0.cnt[p.k];
+    }
+    with_hw(a.hasher, a.width, p.x, [&](auto h, auto w, auto x) {
+        if constexpr (!(x && w == 2))  // (the plan sets x for widths above 2 only)
+            hipLaunchKernelGGL((merkle_climb_kernel<h, w, x>), dim3(p.wgs), dim3(256), 0, a.st, leaves, n, a.width, a.tree,
+                               p.f, a.root, ctr);
+    });
+    return 0;
+}
 
-int launch_merkle_levelwise(int hasher, int width, const uint8_t* d_leaves, uint64_t n, uint8_t* d_tree,
-                            uint8_t* d_root, hipStream_t st);
+static void launch_merkle_two(const MerkleArgs& a, const TreeLevels& t, const MerklePlan::TwoLaunch& p) {
+    with_hw(a.hasher, a.width, p.sm3x, [&](auto h, auto w, auto x) {
+        hipLaunchKernelGGL((merkle_wg_kernel<h, w, x>), dim3(p.grid), dim3(p.threads), 0, a.st, a.leaves, a.n, a.width,
+                           p.kin, static_cast<int>(p.B), a.tree, t, a.root, p.pair);
+    });
+    for (int l = p.kin + 1; l < p.top; ++l)  // wide middle levels: one launch each
+        launch_level(a.hasher, a.width, a.tree + 32ull * (t.pos[l - 1] + 1), t.cnt[l - 1], a.tree + 32ull * (t.pos[l] + 1),
+                     t.cnt[l], a.st);
+    if (p.top < t.nlev)
+        with_hw(a.hasher, a.width, p.sm3x_top, [&](auto h, auto w, auto x) {
+            hipLaunchKernelGGL((merkle_top_kernel<h, w, x>), dim3(1), dim3(1024), 0, a.st, a.width, p.top, a.tree, t,
+                               a.root, p.pair);
+        });
+}
+
+static void launch_merkle_levelwise(const MerkleArgs& a, const TreeLevels& t) {
+    LevelTable lt{};  // (the count kernel's argument: 32-bit counts)
+    lt.nlevels = t.nlev;
+    const uint8_t* in = a.leaves;
+    for (int l = 0; l < t.nlev; ++l) {
+        lt.pos[l] = t.pos[l];
+        lt.count[l] = static_cast<uint32_t>(t.cnt[l]);
+        uint8_t* out = a.tree + 32 * (t.pos[l] + 1);
+        launch_level(a.hasher, a.width, in, l ? t.cnt[l - 1] : a.n, out, t.cnt[l], a.st);
+        in = out;
+    }
+    hipLaunchKernelGGL(merkle_counts_kernel, dim3(1), dim3(64), 0, a.st, a.tree, lt);
+    if (a.root) hipLaunchKernelGGL(copy32_kernel, dim3(1), dim3(64), 0, a.st, in, a.root);
+}
 
 int launch_merkle(int hasher, int width, const uint8_t* d_leaves, uint64_t n, uint8_t* d_tree,
                   uint8_t* d_root, hipStream_t st) {
-    if (n == 0 || width < 2 || width > 64) return BCOSGPU_E_ARG;
-    // A/B switch to the one-launch-per-level path, read once per process
-    static const bool levelwise = [] {
-        const char* lw = getenv("BCOSGPU_MERKLE_LEVELWISE");
-        return lw && atoi(lw) == 1;
-    }();
-    if (levelwise) return launch_merkle_levelwise(hasher, width, d_leaves, n, d_tree, d_root, st);
-    if (n == 1) {  // Merkle.h:177-182
+    const MerkleArgs a{hasher, width, d_leaves, n, d_tree, d_root, st};
+    static const MerkleSwitches sw = parse_merkle_switches();  // once per process, at the first root
+    const MerklePlan p = plan_merkle(hasher, width, n, static_cast<uint64_t>(cu_count()), sw);
+    if (p.kind == MerklePlan::kArgError) return BCOSGPU_E_ARG;
+    if (p.kind == MerklePlan::kCopy) {
         hipLaunchKernelGGL(copy32_kernel, dim3(1), dim3(64), 0, st, d_leaves, d_tree);
         if (d_root) hipLaunchKernelGGL(copy32_kernel, dim3(1), dim3(64), 0, st, d_leaves, d_root);
-        return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
     }
-    TreeLevels t{};
-    uint64_t pos = 0;
-    for (uint64_t m = n; m > 1;) {
-        if (t.nlev >= 64) return BCOSGPU_E_ARG;
-        m = (m + width - 1) / width;
-        t.pos[t.nlev] = pos;
-        t.cnt[t.nlev] = m;
-        pos += m + 1;
-        ++t.nlev;
+    for (int i = 0, rc = 1; i < p.npaths && rc == 1; ++i) {
+        rc = 0;
+        if (p.paths[i] == kPathClimb) rc = launch_merkle_climb(a, p.t, p.climb);
+        else if (p.paths[i] == kPathFused) rc = launch_merkle_fused(a, p.fused);
+        else if (p.paths[i] == kPathTwoLaunch) launch_merkle_two(a, p.t, p.two);
+        else launch_merkle_levelwise(a, p.t);
     }
-    // latency-sized trees: one launch, one wave per workgroup (BCOSGPU_MERKLE_FUSED=0/1 forces it off/on)
-    static const int fused_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_FUSED");
-        return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
-    }();
-    // narrow Keccak trees: the four-wave one-launch kernel (BCOSGPU_MERKLE_CLIMB=0/1 forces it off/on)
-    static const int climb_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_CLIMB");
-        return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
-    }();
-    // Throughput-sized trees (more level-1 nodes than 256 per CU), where the subtree kernel runs first,
-    // take it at every width up to 16 and both hashers (16M leaves, width 16: Keccak 0.62 vs 0.94 ms on
-    // the two-launch path, SM3 0.56 vs 0.71, profiles/r04_merkle_paths_ab_w16.json); at latency sizes
-    // only narrow Keccak trees (SM3's one-lane levels measured no faster than the two-launch path,
-    // profiles/r04_merkle_paths_ab_sm3.json; width 16 has the one-wave kernel)
-    const bool big = t.cnt[0] > 256ull * static_cast<uint64_t>(cu_count());
-    // SM3 trees of width > 2 at latency sizes (C1: 100k leaves, width 16) on the climb kernel with expanded
-    // blocks -- one launch instead of merkle_wg_kernel + merkle_top_kernel -- measured no faster (C1 SM3
-    // 0.1058 vs 0.1038 ms, profiles/r06_merkle_sm3_climbx_ab.json: the critical path is 38 serial
-    // compressions either way, and the second launch's gap is a few us), so it is opt-in
-    // (BCOSGPU_MERKLE_SM3CLIMB=1, read once)
-    static const bool sm3climb_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_SM3CLIMB");
-        return e && e[0] == '1';
-    }();
-    const bool sm3_climb = hasher == SM3 && width > 2 && !big && sm3climb_env;
-    if (fused_env != 1 &&
-        (climb_env == 1 || sm3_climb ||
-         (climb_env < 0 && ((width <= kClimbMaxWidth && (hasher == KECCAK256 || big)) || (width <= 16 && big))))) {
-        const int rc = launch_merkle_climb(hasher, width, d_leaves, n, d_tree, d_root, t, st, sm3_climb);
-        if (rc <= 0) return rc;
-    }
-    if (fused_env == 1 || (fused_env < 0 && hasher == KECCAK256)) {
-        const int rf = launch_merkle_fused(hasher, width, d_leaves, n, d_tree, d_root, t, fused_env == 1, st);
-        if (rf <= 0) return rf;
-    }
-    int kin = 0;
-    uint32_t B = 1;
-    while (B * static_cast<uint32_t>(width) <= 256u) {
-        B *= width;
-        ++kin;
-    }
-    const dim3 g1(static_cast<unsigned>((t.cnt[0] + B - 1) / B));
-    // Keccak levels on lane pairs while level 1 is latency-sized: at most one pair per lane of a wave
-    // per SIMD (kPairMaxNodes); beyond that one lane per node, which issues fewer instructions per node.
-    // BCOSGPU_MERKLE_PAIR=0/1 forces it off/on (A/B), read once per process.
-    static const int pair_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_PAIR");
-        return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
-    }();
-    const int pair = hasher == KECCAK256 && (pair_env >= 0 ? pair_env : t.cnt[0] <= kPairMaxNodes) ? 1 : 0;
-    // Keccak: enough 32-lane groups that the second level runs one cooperative pass (B / width nodes),
-    // two lanes per level-1 node in pair mode
-    uint32_t threads = pair ? 2u * B : B;
-    if (hasher == KECCAK256 && kin >= 1 && 32u * (B / width) > threads && 32u * (B / width) <= 512u) threads = 32u * (B / width);
-    const dim3 b1(threads);
-    // SM3 at latency sizes (a workgroup per CU at most): the LDS levels' and the top kernel's blocks
-    // expanded in parallel (sm3_level_x; its 70 KB of LDS would cost a throughput-sized level 1 occupancy).
-    // BCOSGPU_MERKLE_SM3X=0/1 forces it off/on (A/B), read once per process.
-    static const int sm3x_env = [] {
-        const char* e = getenv("BCOSGPU_MERKLE_SM3X");
-        return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
-    }();
-    const bool sm3x = hasher == SM3 && (sm3x_env >= 0 ? sm3x_env == 1 : g1.x <= static_cast<unsigned>(cu_count()));
-    const bool sm3x_top = hasher == SM3 && sm3x_env != 0;
-#define WG(HH, WW, XX) hipLaunchKernelGGL((merkle_wg_kernel<HH, WW, XX>), g1, b1, 0, st, d_leaves, n, width, kin, static_cast<int>(B), d_tree, t, d_root, pair)
-    if (hasher == SM3) {
-        if (sm3x) {
-            if (width == 2) WG(SM3, 2, true); else if (width == 16) WG(SM3, 16, true); else WG(SM3, 0, true);
-        } else {
-            if (width == 2) WG(SM3, 2, false); else if (width == 16) WG(SM3, 16, false); else WG(SM3, 0, false);
-        }
-    } else {
-        if (width == 2) WG(KECCAK256, 2, false); else if (width == 16) WG(KECCAK256, 16, false); else WG(KECCAK256, 0, false);
-    }
-#undef WG
-    int l = kin + 1;  // next level (0-based) to compute
-    while (l < t.nlev && t.cnt[l - 1] > kTopKernelMaxIn) {  // wide middle levels: one launch each
-        launch_level(hasher, width, d_tree + 32ull * (t.pos[l - 1] + 1), t.cnt[l - 1], d_tree + 32ull * (t.pos[l] + 1),
-                     t.cnt[l], st);
-        ++l;
-    }
-    if (l < t.nlev) {
-#define TOP(HH, WW, XX) hipLaunchKernelGGL((merkle_top_kernel<HH, WW, XX>), dim3(1), dim3(1024), 0, st, width, l, d_tree, t, d_root, pair)
-        if (hasher == SM3) {
-            if (sm3x_top) {
-                if (width == 2) TOP(SM3, 2, true); else if (width == 16) TOP(SM3, 16, true); else TOP(SM3, 0, true);
-            } else {
-                if (width == 2) TOP(SM3, 2, false); else if (width == 16) TOP(SM3, 16, false); else TOP(SM3, 0, false);
-            }
-        } else {
-            if (width == 2) TOP(KECCAK256, 2, false); else if (width == 16) TOP(KECCAK256, 16, false); else TOP(KECCAK256, 0, false);
-        }
-#undef TOP
-    }
-    return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
-}
-
-int launch_merkle_levelwise(int hasher, int width, const uint8_t* d_leaves, uint64_t n, uint8_t* d_tree,
-                            uint8_t* d_root, hipStream_t st) {
-    if (n == 0 || width < 2 || width > 64) return BCOSGPU_E_ARG;
-    if (n == 1) {
-        hipLaunchKernelGGL(copy32_kernel, dim3(1), dim3(64), 0, st, d_leaves, d_tree);
-        if (d_root) hipLaunchKernelGGL(copy32_kernel, dim3(1), dim3(64), 0, st, d_leaves, d_root);
-        return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
-    }
-    LevelTable t{};
-    uint64_t pos = 0, nin = n;
-    const uint8_t* in = d_leaves;
-    while (nin > 1) {
-        const uint64_t nout = (nin + width - 1) / width;
-        if (t.nlevels >= 64) return BCOSGPU_E_ARG;
-        t.pos[t.nlevels] = pos;
-        t.count[t.nlevels] = static_cast<uint32_t>(nout);
-        ++t.nlevels;
-        uint8_t* out = d_tree + 32 * (pos + 1);
-        launch_level(hasher, width, in, nin, out, nout, st);
-        in = out;
-        pos += nout + 1;
-        nin = nout;
-    }
-    hipLaunchKernelGGL(merkle_counts_kernel, dim3(1), dim3(64), 0, st, d_tree, t);
-    if (d_root) hipLaunchKernelGGL(copy32_kernel, dim3(1), dim3(64), 0, st, d_tree + 32 * (pos - 1), d_root);
     return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
 }
 
@@ -1235,13 +1036,9 @@ int launch_merkle_roots_batch(int hasher, int width, const uint8_t* d_leaves, co
             t.out_off[nb] = o;
             uint8_t* out = (l + 1 == L) ? d_roots + 32ull * c0 : d_work + ((l & 1) ? half : 0);
             dim3 g(grid_for(o, 256)), blk(256);
-#define SEG(HH, WW) hipLaunchKernelGGL((merkle_seg_level_kernel<HH, WW>), g, blk, 0, st, in, width, out, t)
-            if (hasher == SM3) {
-                if (width == 2) SEG(SM3, 2); else if (width == 16) SEG(SM3, 16); else SEG(SM3, 0);
-            } else {
-                if (width == 2) SEG(KECCAK256, 2); else if (width == 16) SEG(KECCAK256, 16); else SEG(KECCAK256, 0);
-            }
-#undef SEG
+            with_hw(hasher, width, false, [&](auto h, auto w, auto) {
+                hipLaunchKernelGGL((merkle_seg_level_kernel<h, w>), g, blk, 0, st, in, width, out, t);
+            });
             in = out;
             for (uint32_t b = 0; b < nb; ++b) t.in_off[b] = t.out_off[b];
         }
@@ -1425,9 +1222,6 @@ int launch_merkle_old(int hasher, const uint8_t* d_leaves, uint64_t n, uint8_t* 
     return hipGetLastError() == hipSuccess ? 0 : BCOSGPU_E_HIP;
 }
 
-}  // namespace bcosgpu
-
-namespace bcosgpu {
 // ------------------------------------------------------------------ the vector<bytes> tree layout
 // BlockImpl::calculateTransactionRoot stores the tree in m_inner->transactionsMerkle, a
 // vector<vector<char>> (BlockImpl.h:136, tars field 9), and merkleBench fills a vector<bytes>

@@ -41,7 +41,7 @@ int main(int argc, char** argv) {
         (void)hipDeviceSynchronize();
         static uint64_t mp[4096][40];
         (void)hipMemcpyFromSymbol(mp, HIP_SYMBOL(g_mp), sizeof(mp));
-        uint64_t S = 1;  // level-1 nodes per wave (launch_merkle_fused: width^a <= 32 for Keccak, <= 64 for SM3)
+        uint64_t S = 1;  // level-1 nodes per wave (plan_fused, merkle_plan.h: width^a <= 32 for Keccak, <= 64 for SM3)
         while (S * width <= (h == KECCAK256 ? 32u : 64u)) S *= width;
         const uint64_t waves = ((n + width - 1) / width + S - 1) / S;
         uint64_t t0 = ~0ull, l0max = 0, innermax = 0, l0sum = 0;

@@ -355,3 +355,68 @@ def test_merkle_sm3_climb_expanded_opt_in(gpu, oracle):
         leaves = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
         _, want = oracle.merkle(1, w, leaves, want_tree=True)
         assert got[spec] == hashlib.sha256(want.tobytes()).hexdigest(), spec
+
+
+# every forced Merkle path (the switch sets of tools/merkle_ab.py PATHS, and the level-by-level path): the
+# non-default ones are what a stream under graph capture, or one past the counter-slot pool, runs
+FORCED_PATHS = {"default": {},
+                "sm3_climbx": {"BCOSGPU_MERKLE_SM3CLIMB": "1"},
+                "climb": {"BCOSGPU_MERKLE_CLIMB": "1"},
+                "fused": {"BCOSGPU_MERKLE_CLIMB": "0", "BCOSGPU_MERKLE_FUSED": "1"},
+                "twolaunch": {"BCOSGPU_MERKLE_CLIMB": "0", "BCOSGPU_MERKLE_FUSED": "0"},
+                "nosub": {"BCOSGPU_MERKLE_NOSUB": "1"},
+                "nosub_lat": {"BCOSGPU_MERKLE_NOSUB": "1", "BCOSGPU_MERKLE_LATSCHED": "1"},
+                "levelwise": {"BCOSGPU_MERKLE_LEVELWISE": "1"}}
+FORCED_PATH_SPECS = [(h, w, n) for h in (0, 1) for w in (2, 16) for n in (2, 4099, 70_001)]
+
+FORCED_PATH_CHILD = r"""
+import os, sys, numpy as np
+sys.path[:0] = [sys.argv[1]]
+import bcos_gpu
+bcos_gpu.ensure_device(0)
+bad = 0
+for spec in sys.argv[3:]:
+    h, w, n = (int(x) for x in spec.split("x"))
+    leaves = np.fromfile(os.path.join(sys.argv[2], "leaves_%d.bin" % n), dtype=np.uint8).reshape(n, 32)
+    with open(os.path.join(sys.argv[2], "tree_%s.bin" % spec), "rb") as f:
+        want = f.read()
+    H = bcos_gpu.SM3() if h else bcos_gpu.Keccak256()
+    got = b"".join(bcos_gpu.Merkle(H, w).generate_merkle([leaves[i].tobytes() for i in range(n)]))
+    if got != want:
+        bad += 1
+        k = next((i for i in range(min(len(got), len(want)) // 32) if got[32 * i:32 * i + 32] != want[32 * i:32 * i + 32]), -1)
+        sys.stdout.write("MISMATCH %s: %d vs %d bytes, first differing entry %d\n" % (spec, len(got), len(want), k))
+sys.exit(1 if bad else 0)
+"""
+
+
+@pytest.fixture(scope="module")
+def forced_path_trees(oracle, tmp_path_factory):
+    """Leaves and the oracle's full output vector per (hasher, width, n), computed once, in files the child reads."""
+    d = tmp_path_factory.mktemp("forced_paths")
+    rng = np.random.default_rng(97)
+    leaves = {}
+    for h, w, n in FORCED_PATH_SPECS:
+        if n not in leaves:
+            leaves[n] = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+            leaves[n].tofile(str(d / ("leaves_%d.bin" % n)))
+        _, want = oracle.merkle(h, w, leaves[n], want_tree=True)
+        want.tofile(str(d / ("tree_%dx%dx%d.bin" % (h, w, n))))
+    return str(d)
+
+
+@pytest.mark.parametrize("path", list(FORCED_PATHS))
+def test_merkle_forced_paths_small(forced_path_trees, path):
+    """Each switch set in a child process (the switches are read once per process): both hashers, widths 2 and 16,
+    n = 2 / 4099 / 70001 (one node; several level-1 workgroups with a ragged last group; a top level above the
+    in-workgroup levels), the whole output vector byte for byte equal to the oracle's tree."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("BCOSGPU_MERKLE_")}
+    env.update(FORCED_PATHS[path])
+    specs = ["%dx%dx%d" % s for s in FORCED_PATH_SPECS]
+    r = subprocess.run([sys.executable, "-c", FORCED_PATH_CHILD, os.path.join(root, "fisco-bcos_amd"), forced_path_trees]
+                       + specs, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
