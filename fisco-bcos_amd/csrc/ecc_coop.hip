@@ -269,15 +269,6 @@ struct CoopLds {
     uint32_t post[2];                 // phase-A hand-off flags: 0 r^-1 ready, 1 e ready
 };
 
-// One-way hand-offs between waves inside phase A: the producer writes its per-lane values, then
-// releases the flag; the consumer acquires it.  Workgroup scope, so these are LDS-only fences.
-__device__ __forceinline__ void coop_post(uint32_t* f) {
-    __hip_atomic_store(f, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void coop_wait(uint32_t* f) {
-    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) __builtin_amdgcn_s_sleep(1);
-}
-
 struct CoopCtx {
     CoopLds* L;
     int chain, role, lane;
@@ -618,19 +609,19 @@ __global__ __launch_bounds__(256, 1) void tx_verify_coop_kernel(const uint8_t* _
         fe_from_be_words(e, d);
         reduce_once(e, ParamN1::M);
         lds_store_fe(L.xe, e, lane);
-        coop_post(&L.post[1]);
+        lds_flag_post(&L.post[1]);
         COOP_T(7);
     } else if (wave == 0) {
         fe rm, rinv;
         FieldN1::from_plain(rm, r);
         FieldInv<FieldN1>::inv(rinv, rm);
         lds_store_fe(L.xrinv, rinv, lane);
-        coop_post(&L.post[0]);
+        lds_flag_post(&L.post[0]);
         COOP_T(7);
     }
     if (wave != 2) {
-        coop_wait(&L.post[0]);
-        coop_wait(&L.post[1]);
+        lds_flag_wait(&L.post[0]);
+        lds_flag_wait(&L.post[1]);
         fe e, rinv, u1;
         lds_load_fe(e, L.xe, lane);
         lds_load_fe(rinv, L.xrinv, lane);
@@ -1226,7 +1217,7 @@ __device__ __forceinline__ void coop26_post_e_inv(LDS& L, const IO& io, uint64_t
         if (active) io.template digest<KECCAK256>(i, e);
         reduce_once(e, ParamN1::M);
         lds_store_fe(L.xe, e, lane);
-        coop_post(&L.post[1]);
+        lds_flag_post(&L.post[1]);
         COOP_T(7);
     } else if (wave == 0) {
         fe rm, rinv;
@@ -1234,7 +1225,7 @@ __device__ __forceinline__ void coop26_post_e_inv(LDS& L, const IO& io, uint64_t
         if constexpr (PIPE) FieldInv<FieldN1>::inv_pipe(rinv, rm);
         else FieldInv<FieldN1>::inv(rinv, rm);
         lds_store_fe(L.xrinv, rinv, lane);
-        coop_post(&L.post[0]);
+        lds_flag_post(&L.post[0]);
         COOP_T(7);
     }
 }
@@ -1243,8 +1234,8 @@ __device__ __forceinline__ void coop26_post_e_inv(LDS& L, const IO& io, uint64_t
 // halves in L.k and L.flags = ok | neg1 << 2 | neg2 << 3.  Every wave that takes comb windows calls it.
 template <bool VERIFY, class LDS>
 __device__ __forceinline__ void coop26_u1_glv(fe& u1, LDS& L, bool ok, const fe& r, const fe& s, int wave, int lane) {
-    coop_wait(&L.post[0]);
-    coop_wait(&L.post[1]);
+    lds_flag_wait(&L.post[0]);
+    lds_flag_wait(&L.post[1]);
     fe e, rinv;
     lds_load_fe(e, L.xe, lane);
     lds_load_fe(rinv, L.xrinv, lane);
@@ -1318,10 +1309,10 @@ template <class LDS>
 __device__ __forceinline__ void coop26_store_partial(LDS& L, const Jac26& G, int wave, int lane) {
     if (wave == 0) {
         coop26_store_jac(L.pt[2], G, lane);
-        coop_post(&L.post[2]);
+        lds_flag_post(&L.post[2]);
     } else if (wave == 3) {
         Jac26 G0, S;
-        coop_wait(&L.post[2]);
+        lds_flag_wait(&L.post[2]);
         coop26_load_jac(G0, L.pt[2], lane);
         CurveK1x::add(S, G0, G);
         coop26_store_jac(L.pt[3], S, lane);
@@ -1576,7 +1567,7 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
     {
         fe u1;
         coop26_u1_glv<false>(u1, L, ok, r, s, wave, lane);
-        if (wave == 1) coop_post(&L.spost[0]);  // phase C may start: the table, Zc, k and the flags
+        if (wave == 1) lds_flag_post(&L.spost[0]);  // phase C may start: the table, Zc, k and the flags
         Jac26 G;
         int lo, hi;
         comb_share(lo, hi, kTrioRecoverShare.wide, wave);
@@ -1584,12 +1575,12 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         else comb_share_range(G, u1, tab, tab_bits, kTrioRecoverShare, wave);
         // no partial is added here: each wave's goes to phase D behind its own flag
         coop26_store_jac(L.pt[wave == 0 ? 3 : wave == 3 ? 4 : wave == 2 ? 0 : 2], G, lane);
-        coop_post(&L.spost[1 + wave]);
+        lds_flag_post(&L.spost[1 + wave]);
     }
     COOP_T(1);
     // each wave enters phase C once wave 1 has posted the table and the scalars; what the other waves leave
     // in LDS is read in phase D only, behind their own flags or a barrier
-    coop_wait(&L.spost[0]);
+    lds_flag_wait(&L.spost[0]);
     // ---------------------------------------------------------------- phase C: one GLV chain per trio
     const TrioLane T(lane);
     const TrioSeat seat(wave, lane, T);
@@ -1625,22 +1616,22 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
     fe26_zero(zi3);
     if (chain == 1) {  // its chain's point to the partner; T = the sum of phase A's comb partials
         trio_store(xbuf, acc, lane);
-        coop_post(&L.spost[5 + (wave >> 1)]);
-        coop_wait(&L.spost[1 + 0]);
-        coop_wait(&L.spost[1 + 3]);
-        if constexpr (kWave2Adds) coop_wait(&L.spost[1 + 2]);
-        if constexpr (kWave1Adds) coop_wait(&L.spost[1 + 1]);
+        lds_flag_post(&L.spost[5 + (wave >> 1)]);
+        lds_flag_wait(&L.spost[1 + 0]);
+        lds_flag_wait(&L.spost[1 + 3]);
+        if constexpr (kWave2Adds) lds_flag_wait(&L.spost[1 + 2]);
+        if constexpr (kWave1Adds) lds_flag_wait(&L.spost[1 + 1]);
         TrioPt A;
         trio_sum_partials<kWave2Adds, kWave1Adds>(A, L, tl, T);
         trio_store(gbuf, A, lane);
     } else {  // S = k1 R' + k2 phi(R') for the partner, and its X K, Z K here
         TrioPt P1;
-        coop_wait(&L.spost[5 + (wave >> 1)]);
+        lds_flag_wait(&L.spost[5 + (wave >> 1)]);
         trio_load(P1, xbuf, lane);
         trio_add(acc, acc, P1, T);
         trio_store(xbuf, acc, lane);
         fe26 zc, w, K;
-        coop_wait(&L.spost[1 + 2]);  // w is wave 2's (stored before its comb partial)
+        lds_flag_wait(&L.spost[1 + 2]);  // w is wave 2's (stored before its comb partial)
         load_zc_w(zc, w);
         fe26_sqr(K, zc);
         fe26_mul(K, K, w);

@@ -121,6 +121,26 @@ __device__ __forceinline__ void shl1(fe& k) {
     for (int i = 7; i > 0; --i) k.v[i] = __builtin_amdgcn_alignbit(k.v[i], k.v[i - 1], 31);
     k.v[0] <<= 1;
 }
+__device__ __forceinline__ void shl4_128(fe& k) {
+#pragma unroll
+    for (int i = 3; i > 0; --i) k.v[i] = __builtin_amdgcn_alignbit(k.v[i], k.v[i - 1], 28);
+    k.v[0] <<= 4;
+}
+// one Booth digit (-8 .. 8) of a 256-bit scalar, window at bits 252..255: the window's value plus the bit
+// below it, minus 16 when the window's top bit is set; k moves up by one window
+__device__ __forceinline__ int booth_digit256(fe& k) {
+    const uint32_t top = k.v[7];
+    const uint32_t W = top >> 28, c = (top >> 27) & 1u;
+    shl4(k);
+    return static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
+}
+// one Booth digit of a 128-bit scalar held in k.v[0..3], window at bits 124..127
+__device__ __forceinline__ int booth_digit128(fe& k) {
+    const uint32_t top = k.v[3];
+    const uint32_t W = top >> 28, c = (top >> 27) & 1u;
+    shl4_128(k);
+    return static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
+}
 // x mod n for x < 2^256 (n > 2^255)
 __device__ __forceinline__ void reduce_once(fe& x, const uint32_t* n) {
     fe t;
@@ -208,10 +228,7 @@ __device__ __forceinline__ void booth_mul(Jac& acc, const fe& k_plain, const Aff
         C::dbl(acc, acc);
         C::dbl(acc, acc);
         C::dbl(acc, acc);
-        const uint32_t top = k.v[7];
-        const uint32_t W = top >> 28, c = (top >> 27) & 1u;
-        const int d = static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
-        shl4(k);
+        const int d = booth_digit256(k);
         const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
         Jac S;
         fe_copy(S.X, T[0].X); fe_copy(S.Y, T[0].Y); fe_copy(S.Z, T[0].Z); S.inf = false;
@@ -269,20 +286,6 @@ __device__ __forceinline__ void glv_split(fe& k1, bool& neg1, fe& k2, bool& neg2
     neg2 = fe_lt(half, k2);
     FieldN1::neg(nk, k2);
     fe_cmov(k2, nk, neg2);
-}
-
-__device__ __forceinline__ void shl4_128(fe& k) {
-#pragma unroll
-    for (int i = 3; i > 0; --i) k.v[i] = __builtin_amdgcn_alignbit(k.v[i], k.v[i - 1], 28);
-    k.v[0] <<= 4;
-}
-
-// one Booth digit of a 128-bit scalar held in k.v[0..3], window at bits 124..127
-__device__ __forceinline__ int booth_digit128(fe& k) {
-    const uint32_t top = k.v[3];
-    const uint32_t W = top >> 28, c = (top >> 27) & 1u;
-    shl4_128(k);
-    return static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
 }
 
 // acc += (sign * d) * (phi ? lambda : 1) * P over an affine table T[j] = (j+1) P (mixed add)
@@ -496,10 +499,7 @@ __device__ __forceinline__ void booth_mul_sm2(Jac& acc, const fe& k_plain, const
             CurveSM2::dbl(acc, acc);
             CurveSM2::dbl(acc, acc);
             CurveSM2::dbl(acc, acc);
-            const uint32_t top = k.v[7];
-            const uint32_t W = top >> 28, c = (top >> 27) & 1u;
-            const int d = static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
-            shl4(k);
+            const int d = booth_digit256(k);
             add_digit_ldsx<CurveSM2, FieldP2>(acc, ldsx, Y, d, false, false);
         }
         return;
@@ -511,12 +511,20 @@ __device__ __forceinline__ void booth_mul_sm2(Jac& acc, const fe& k_plain, const
         CurveSM2::dbl(acc, acc);
         CurveSM2::dbl(acc, acc);
         CurveSM2::dbl(acc, acc);
-        const uint32_t top = k.v[7];
-        const uint32_t W = top >> 28, c = (top >> 27) & 1u;
-        const int d = static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
-        shl4(k);
+        const int d = booth_digit256(k);
         add_digit_aff<CurveSM2, FieldP2>(acc, A, d, false, false);
     }
+}
+
+// One-way hand-offs between the waves of a workgroup through a flag in LDS: the producer writes its
+// values, then posts (a release store of 1); the consumer waits (acquire loads, s_sleep between them).
+// Workgroup scope, so these are LDS-only fences.  A post by every lane of a wave releases each lane's
+// own stores; a post by one lane alone must follow a workgroup release fence executed by the wave.
+__device__ __forceinline__ void lds_flag_post(uint32_t* f) {
+    __hip_atomic_store(f, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void lds_flag_wait(uint32_t* f) {
+    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) __builtin_amdgcn_s_sleep(1);
 }
 
 // per-lane field elements and points in LDS, [word][lane] (conflict-free)

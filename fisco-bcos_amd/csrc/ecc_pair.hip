@@ -35,9 +35,11 @@ struct Sm2PairLds {
 // One pair of waves: each exchange writes the caller's slots of the current parity, publishes its
 // sequence number, waits for the partner's, reads the partner's slots and flips parity.  A parity's
 // slots are rewritten only after the partner has published the NEXT exchange, i.e. after it has read
-// them.
+// them.  One context for both pair kernels (Lds = Sm2PairLds or Sm2Pair26Lds): an element travels as the
+// LDS struct's ex[] packs it, an fe as 2 x uint4, an fp26 as 5 x uint2 (raw limbs).
+template <class Lds>
 struct PairCtx {
-    Sm2PairLds* L;
+    Lds* L;
     int role, lane;
     uint32_t seq;
     int par;
@@ -52,6 +54,20 @@ struct PairCtx {
         a.v[0] = q0.x; a.v[1] = q0.y; a.v[2] = q0.z; a.v[3] = q0.w;
         a.v[4] = q1.x; a.v[5] = q1.y; a.v[6] = q1.z; a.v[7] = q1.w;
     }
+    __device__ __forceinline__ void put(int s, const fp26& a) const {
+        uint2* p = &L->ex[par][role][s][0][0] + lane;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) p[q * 64] = make_uint2(a.v[2 * q], a.v[2 * q + 1]);
+    }
+    __device__ __forceinline__ void get(int s, fp26& a) const {
+        const uint2* p = &L->ex[par][role ^ 1][s][0][0] + lane;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            const uint2 w = p[q * 64];
+            a.v[2 * q] = w.x;
+            a.v[2 * q + 1] = w.y;
+        }
+    }
     __device__ __forceinline__ void sync() {
         ++seq;
         __hip_atomic_store(&L->seq[role], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -60,9 +76,10 @@ struct PairCtx {
     }
     __device__ __forceinline__ void next() { par ^= 1; }
 };
+using Pair32Ctx = PairCtx<Sm2PairLds>;
 
 // P = 2 P on SM2 (a = -3, dbl-2001-b with Z3 = 2 Y Z), P replicated on both waves of the pair
-__device__ __forceinline__ void pair_dbl_am3(Jac& P, PairCtx& c) {
+__device__ __forceinline__ void pair_dbl_am3(Jac& P, Pair32Ctx& c) {
     using F = FieldP2;
     fe alpha, A2, b4, g8, X3, Y3, Z3, t, u;
     if (c.role == 0) {
@@ -117,7 +134,7 @@ __device__ __forceinline__ void pair_dbl_am3(Jac& P, PairCtx& c) {
 
 // R = P + Q (madd-2007-bl with the complete-addition special cases of Curve::madd), Q affine
 template <class F, class C>
-__device__ __forceinline__ void pair_madd(Jac& R, const Jac& P, const Aff& Q, PairCtx& c) {
+__device__ __forceinline__ void pair_madd(Jac& R, const Jac& P, const Aff& Q, Pair32Ctx& c) {
     fe Z1Z1, H, HH, Z3, rr, R2, I, J, V, X3, Y3, t, u;
     F::sqr(Z1Z1, P.Z);
     if (c.role == 0) {
@@ -200,7 +217,7 @@ __device__ __forceinline__ void pair_madd(Jac& R, const Jac& P, const Aff& Q, Pa
     }
 }
 
-__device__ __forceinline__ void pair_add_digit_sm2(Jac& acc, PairCtx& c, int d) {
+__device__ __forceinline__ void pair_add_digit_sm2(Jac& acc, Pair32Ctx& c, int d) {
     const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
     const uint32_t* base = &c.L->tab[0][0][0] + m * (16 * 64) + c.lane;
     Aff S;
@@ -314,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair_kernel(const uint8_
     FieldP2::from_plain(P.y, py);
     Jac acc;
     if (wave <= 1) {
-        PairCtx c{&L, wave, lane, 0u, 0};
+        Pair32Ctx c{&L, wave, lane, 0u, 0};
         if (wave == 0) {
             Aff A[8];
             sm2_affine_table(A, P);
@@ -335,10 +352,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair_kernel(const uint8_
             pair_dbl_am3(acc, c);
             pair_dbl_am3(acc, c);
             pair_dbl_am3(acc, c);
-            const uint32_t top = k.v[7];
-            const uint32_t W = top >> 28, cb = (top >> 27) & 1u;
-            const int d = static_cast<int>(W + cb) - static_cast<int>((W >> 3) << 4);
-            shl4(k);
+            const int d = booth_digit256(k);
             pair_add_digit_sm2(acc, c, d);
         }
     } else if (wave == 2) {
@@ -371,9 +385,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair_kernel(const uint8_
         for (int k = 0; k < 5; ++k) L.addr[k][lane] = ad[k];
         Jac G0, G1, G;
         comb_range8<CurveSM2>(G0, s, tab, 0, 16);
-        while (__hip_atomic_load(&L.seq[2], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
-            __builtin_amdgcn_s_sleep(1);
-        }
+        lds_flag_wait(&L.seq[2]);
         pair_load_jac(G1, L.gh, lane);
         CurveSM2::add(G, G0, G1);
         pair_store_jac(L.g, G, lane);
@@ -381,7 +393,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair_kernel(const uint8_
         Jac G1;
         comb_range8<CurveSM2>(G1, s, tab, 16, 32);
         pair_store_jac(L.gh, G1, lane);
-        __hip_atomic_store(&L.seq[2], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        lds_flag_post(&L.seq[2]);
     }
     __syncthreads();
     if (wave == 0 && active) {
@@ -426,33 +438,7 @@ struct Sm2Pair26Lds {
     uint32_t seq[4];
 };
 
-struct Pair26Ctx {
-    Sm2Pair26Lds* L;
-    int role, lane;
-    uint32_t seq;
-    int par;
-    __device__ __forceinline__ void put(int s, const fp26& a) const {
-        uint2* p = &L->ex[par][role][s][0][0] + lane;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) p[q * 64] = make_uint2(a.v[2 * q], a.v[2 * q + 1]);
-    }
-    __device__ __forceinline__ void get(int s, fp26& a) const {
-        const uint2* p = &L->ex[par][role ^ 1][s][0][0] + lane;
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            const uint2 w = p[q * 64];
-            a.v[2 * q] = w.x;
-            a.v[2 * q + 1] = w.y;
-        }
-    }
-    __device__ __forceinline__ void sync() {
-        ++seq;
-        __hip_atomic_store(&L->seq[role], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        while (__hip_atomic_load(&L->seq[role ^ 1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq) {
-        }
-    }
-    __device__ __forceinline__ void next() { par ^= 1; }
-};
+using Pair26Ctx = PairCtx<Sm2Pair26Lds>;
 
 // as pair_dbl_am3 with CurveSM2x::dbl's magnitudes (X <= 5, Y, Z <= 8 -> (2, 2, 2)):
 //   a: alpha = 3 (X - d)(X + d) (3), alpha^2 (1) | b: 4 beta (4), 8 gamma^2 (8)
@@ -613,6 +599,16 @@ __device__ __forceinline__ void pair26_madd(JacP26& R, const JacP26& P, const Af
     }
 }
 
+// the sign of a table entry for Booth digit d on fp26: y (m 1) <- -y when d < 0, weakly normalised.  Shared
+// by the fetches of the pair kernel (pair26_add_digit) and of the trio kernel (trio_table_entry, the
+// Jacobian entry of trio_add_digit_sm2_jd)
+__device__ __forceinline__ void entry_sign26(fp26& y, int d) {
+    fp26 ny;
+    fp26_neg<2>(ny, y);
+    fp26_cmov(y, ny, d < 0);
+    fp26_normalize_weak(y);
+}
+
 __device__ __forceinline__ void pair26_add_digit(JacP26& acc, Pair26Ctx& c, int d) {
     const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
     const uint32_t* base = &c.L->tab[0][0][0] + m * (16 * 64) + c.lane;
@@ -627,10 +623,7 @@ __device__ __forceinline__ void pair26_add_digit(JacP26& acc, Pair26Ctx& c, int 
         fp26_from_words(S.x, x);
         fp26_from_words(S.y, y);
     }
-    fp26 ny;
-    fp26_neg<2>(ny, S.y);
-    fp26_cmov(S.y, ny, d < 0);
-    fp26_normalize_weak(S.y);
+    entry_sign26(S.y, d);
     JacP26 R;
     pair26_madd(R, acc, S, c);
     CurveSM2x::cmov(acc, R, d != 0);
@@ -728,6 +721,9 @@ __device__ __forceinline__ void pair26_load_jac(JacP26& P, const uint32_t (*src)
     P.inf = src[24][lane] != 0u;
 }
 
+// the slots of L.seq[] in the fp26 kernels (the table of who posts and who waits: at Sm2Trio26Lds)
+enum Sm2Seq : int { kSeqJacTab0 = 0, kSeqJacTab1 = 1, kSeqCombHalf = 2, kSeqAffineTab = 3, kSeqLowSum = 4 };
+
 template <class IO>
 __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair26_kernel(IO io, uint64_t n, const uint32_t* __restrict__ tab) {
     __shared__ Sm2Pair26Lds L;
@@ -787,10 +783,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair26_kernel(IO io, uin
             pair26_dbl(acc, c);
             pair26_dbl(acc, c);
             pair26_dbl(acc, c);
-            const uint32_t top = k.v[7];
-            const uint32_t W = top >> 28, cb = (top >> 27) & 1u;
-            const int d = static_cast<int>(W + cb) - static_cast<int>((W >> 3) << 4);
-            shl4(k);
+            const int d = booth_digit256(k);
             pair26_add_digit(acc, c, d);
         }
     } else if (wave == 2) {
@@ -812,9 +805,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair26_kernel(IO io, uin
         for (int k = 0; k < 5; ++k) L.addr[k][lane] = ad[k];
         JacP26 G0, G1, G;
         comb_range_sm2_26(G0, s, tab, 0, 16);
-        while (__hip_atomic_load(&L.seq[2], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
-            __builtin_amdgcn_s_sleep(1);
-        }
+        lds_flag_wait(&L.seq[kSeqCombHalf]);
         pair26_load_jac(G1, L.gh, lane);
         CurveSM2x::add(G, G0, G1);
         pair26_store_jac(L.g, G, lane);
@@ -822,7 +813,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair26_kernel(IO io, uin
         JacP26 G1;
         comb_range_sm2_26(G1, s, tab, 16, 32);
         pair26_store_jac(L.gh, G1, lane);
-        __hip_atomic_store(&L.seq[2], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        lds_flag_post(&L.seq[kSeqCombHalf]);
     }
     __syncthreads();
     if (wave == 0 && active) {
@@ -854,9 +845,10 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_pair26_kernel(IO io, uin
 }
 // ------------------------------------------------------------------ SM2 lane-trio kernel (fp26)
 // tx_verify_sm2_pair26_kernel with the t*P chain on lane trios (ecp26_trio.h) instead of a wave pair:
-// 40 txs per workgroup; waves 0 and 1 both build the affine tables of all 40 txs (identical values, so
-// neither waits for the other) and then run the chains of txs 0..19 / 20..39, three lanes per tx;
-// waves 2 and 3 hash, derive e and the address and run the two s*G comb halves as in the pair kernel.
+// 40 txs per workgroup; waves 0 and 1 run the high chains of txs 0..19 / 20..39, three lanes per tx; waves
+// 2 and 3 build those txs' Jacobian tables on their own trios, then wave 2 hashes and derives e and the
+// address while wave 3 turns the Jacobian tables into the affine one, both run their
+// s*G comb halves as in the pair kernel, then the low chains (sm2_low_chain), and wave 2 sums.
 // The chain's additions skip the P = +-Q tests (trio_madd_sm2<false>): the accumulator is K P with
 // |K| >= 16 before each addition of |d| P, |d| <= 8, and |K| < n, so K = +-d (mod n) cannot occur for
 // a P of order n (SM2's cofactor is 1; a P off the curve fails its verdict).  Bit-identical to
@@ -869,9 +861,6 @@ __device__ uint64_t g_sm2_t[4][8];
     if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) g_sm2_t[threadIdx.x >> 6][k] = clock64()
 // low Booth windows of t P per tx run by waves 2 and 3 (sm2_low_chain)
 static constexpr int kSm2TrioSplit = 44;
-#ifndef kSm2DblUnroll
-#define kSm2DblUnroll 1  // doublings per window unrolled in the chain loops (1 = rolled)
-#endif
 struct Sm2Trio26Lds {
     uint32_t tab[8][20][64];         // affine 1P..8P in the R' domain as fp26 limbs: [entry][x, y][tx]
     uint32_t jtab[8][50][40];        // Jacobian 1P..8P: [entry][X, Y, Z, Z^2, Z^3][tx]
@@ -884,14 +873,29 @@ struct Sm2Trio26Lds {
     uint32_t ok2[64];
     uint32_t kb[8][64];              // t again (waves 2 and 3 write it for their own low-window chains)
     uint32_t bacc[25][64];           // the low-window chains' results (canonical X, Y, Z, inf)
-    uint32_t seq[8];
+    uint32_t seq[8];                 // the hand-off flags below (0 at the start, posted once)
 };
 
-__device__ __forceinline__ void trio_add_digit_sm2(TrioPtP& acc, const Sm2Trio26Lds& L, int tl, int d,
-                                                   const TrioLane& T) {
+// The kernel's one-way hand-offs, L.seq[Sm2Seq] (a release store of 1, acquire loads with s_sleep between);
+// the pair kernels have kSeqCombHalf alone (their seq[0] and seq[1] are PairCtx's counters):
+//   flag                posted by                              awaited by                 guards
+//   kSeqJacTab0 + cw    wave 2 + cw, lane 0, after its         chain wave cw before       L.jtab[1..7] of txs
+//                       lds_wave_sync                          window 63's addition;      cw * 20 .. + 19
+//                                                              wave 3 (both flags)
+//   kSeqCombHalf        wave 3, every lane, after its          wave 2 before it sums      L.gh; and, wave 3 having
+//                       stores to L.gh                         the comb halves            built it before, all of L.tab
+//   kSeqAffineTab       wave 3, lane 0, after a release        polled (not awaited) by    L.tab[1..7]: the chains
+//                       fence                                  the chain waves per window switch to the affine entries
+//   kSeqLowSum          wave 3, lane 0, after a release        wave 2 before it adds      L.bacc of txs 20 .. 39
+//                       fence behind its sm2_low_chain         the low sums
+// L.acc, L.g, L.c, L.ok2 and L.addr reach wave 0's verdict through the final __syncthreads.
+
+// S = sign(d) * (|d| P) of tx tl from the affine table L.tab (entry (|d| - 1) & 7; d = 0 reads entry 7 and
+// the caller drops the sum).  Called by every wave's trio lanes (all three lanes of a trio read the same
+// entry); reads L.tab only, which must be complete (entry 0: from the start; all: kSeqAffineTab)
+__device__ __forceinline__ void trio_table_entry(AffP26& S, const Sm2Trio26Lds& L, int tl, int d) {
     const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
     const uint32_t* base = &L.tab[0][0][0] + m * (20 * 64) + tl;
-    AffP26 S;
 #pragma unroll
     for (int q = 0; q < 10; ++q) {
         S.x.v[q] = base[q * 64];
@@ -899,10 +903,13 @@ __device__ __forceinline__ void trio_add_digit_sm2(TrioPtP& acc, const Sm2Trio26
     }
     F26_SETM(S.x, 1);
     F26_SETM(S.y, 1);
-    fp26 ny;
-    fp26_neg<2>(ny, S.y);
-    fp26_cmov(S.y, ny, d < 0);
-    fp26_normalize_weak(S.y);
+    entry_sign26(S.y, d);
+}
+
+__device__ __forceinline__ void trio_add_digit_sm2(TrioPtP& acc, const Sm2Trio26Lds& L, int tl, int d,
+                                                   const TrioLane& T) {
+    AffP26 S;
+    trio_table_entry(S, L, tl, d);
     TrioPtP R;
     trio_madd_sm2<false>(R, acc, S, T);
     trio_cmov_sm2(acc, R, d != 0);
@@ -911,20 +918,8 @@ __device__ __forceinline__ void trio_add_digit_sm2(TrioPtP& acc, const Sm2Trio26
 // the window's addition on the delta-carrying chain (trio_madd_sm2_d): D = Z^2 on lane 0 in and out
 __device__ __forceinline__ void trio_add_digit_sm2_d(TrioPtP& acc, fp26& D, const Sm2Trio26Lds& L, int tl, int d,
                                                      const TrioLane& T) {
-    const uint32_t m = static_cast<uint32_t>((d < 0 ? -d : d) - 1) & 7u;
-    const uint32_t* base = &L.tab[0][0][0] + m * (20 * 64) + tl;
     AffP26 S;
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-        S.x.v[q] = base[q * 64];
-        S.y.v[q] = base[(10 + q) * 64];
-    }
-    F26_SETM(S.x, 1);
-    F26_SETM(S.y, 1);
-    fp26 ny;
-    fp26_neg<2>(ny, S.y);
-    fp26_cmov(S.y, ny, d < 0);
-    fp26_normalize_weak(S.y);
+    trio_table_entry(S, L, tl, d);
     TrioPtP R;
     fp26 Dn;
     trio_madd_sm2_d(R, Dn, acc, D, S, T);
@@ -951,10 +946,7 @@ __device__ __forceinline__ void trio_add_digit_sm2_jd(TrioPtP& acc, fp26& D, con
     F26_SETM(E.Z, 1);
     F26_SETM(E.ZZ, 1);
     F26_SETM(E.ZZZ, 1);
-    fp26 ny;
-    fp26_neg<2>(ny, E.Y);
-    fp26_cmov(E.Y, ny, d < 0);
-    fp26_normalize_weak(E.Y);
+    entry_sign26(E.Y, d);
     TrioPtP R;
     fp26 Dn;
     trio_add_sm2_jd(R, Dn, acc, D, E, T);
@@ -1016,20 +1008,14 @@ __device__ __forceinline__ void sm2_low_chain(Sm2Trio26Lds& L, int wave, int lan
     fp26 D;
     fp26_set(D, p26::ONE_R);
     {
-        const uint32_t top = k.v[7];
-        const uint32_t W = top >> 28, cb = (top >> 27) & 1u;
-        const int d = static_cast<int>(W + cb) - static_cast<int>((W >> 3) << 4);
-        shl4(k);
+        const int d = booth_digit256(k);
         trio_add_digit_sm2(acc, L, tl, d, T);  // to infinity: the table point (D = 1) or infinity
     }
 #pragma unroll 1
     for (int w = split - 2; w >= 0; --w) {
-#pragma unroll kSm2DblUnroll
+#pragma unroll 1
         for (int q = 0; q < 4; ++q) trio_dbl_sm2_d(acc, D, T);
-        const uint32_t top = k.v[7];
-        const uint32_t W = top >> 28, cb = (top >> 27) & 1u;
-        const int d = static_cast<int>(W + cb) - static_cast<int>((W >> 3) << 4);
-        shl4(k);
+        const int d = booth_digit256(k);
         trio_add_digit_sm2_d(acc, D, L, tl, d, T);
     }
     JacP26 J;
@@ -1037,6 +1023,13 @@ __device__ __forceinline__ void sm2_low_chain(Sm2Trio26Lds& L, int wave, int lan
     if (T.r0 && real) pair26_store_jac(L.bacc, J, tl);
 }
 
+// One body, with its prologue, scalar work, verdict, waits and posts written out: this kernel's speed moves
+// with any change of its generated code.  On one MI355X, against 0.582 ms per 10k for c2sm2 and 0.570 ms for
+// 10,240 known-key verifies: built with lds_flag_wait / lds_flag_post alone 0.607 ms (c2sm2); as named
+// phase functions (entry 0, high chain, Jacobian tables, affine table, sums) around written-out waits
+// 0.607 ms; with only a prologue, a scalar-work and a verdict function shared with the pair kernel 0.585
+// and 0.606 ms -- each with the same instruction counts in every chain and comb loop (DESIGN 11,
+// profiles/sm2_bodies_static.json).  So the body keeps the text whose code is measured; the flags are named.
 template <class IO, int SPLIT>
 __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uint64_t n, const uint32_t* __restrict__ tab,
                                                                         int affine, const uint32_t* __restrict__ ctab,
@@ -1121,21 +1114,18 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
 #pragma unroll 1
         for (int w = 63; w >= split; --w) {
             // four doublings, three product levels each (delta carried); rolled: the window's code then
-            // fits the instruction cache far better (kSm2DblRoll)
-#pragma unroll kSm2DblUnroll
+            // fits the instruction cache far better
+#pragma unroll 1
             for (int q = 0; q < 4; ++q) trio_dbl_sm2_d(acc, D, T);
-            const uint32_t top = k.v[7];
-            const uint32_t W = top >> 28, cb = (top >> 27) & 1u;
-            const int d = static_cast<int>(W + cb) - static_cast<int>((W >> 3) << 4);
-            shl4(k);
+            const int d = booth_digit256(k);
             if (w == 63) {  // this wave's Jacobian table (built by wave 2 + this wave) before the first addition
-                while (__hip_atomic_load(&L.seq[wave], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
+                while (__hip_atomic_load(&L.seq[kSeqJacTab0 + wave], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
                     __builtin_amdgcn_s_sleep(1);
                 }
             }
             if (!aff && affine)
                 aff = __builtin_amdgcn_readfirstlane(
-                          __hip_atomic_load(&L.seq[3], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0u;
+                          __hip_atomic_load(&L.seq[kSeqAffineTab], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0u;
             if (aff)
                 trio_add_digit_sm2_d(acc, D, L, tl, d, T);  // four product levels
             else
@@ -1146,7 +1136,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
                                     // measured 5.2k cycles each against 4.3k inside the window loop)
 #pragma unroll 1
             for (int j = split; j > 0; --j) {
-#pragma unroll kSm2DblUnroll
+#pragma unroll 1
                 for (int q = 0; q < 4; ++q) trio_dbl_sm2_d(acc, D, T);
             }
         }
@@ -1219,7 +1209,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
                 // these 20 Jacobian tables are complete: chain wave (wave - 2) may add them and wave 3 build
                 // their affine forms
                 if (lane == 0)
-                    __hip_atomic_store(&L.seq[wave - 2], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_store(&L.seq[kSeqJacTab0 + wave - 2], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
         if (wave == 2) {
@@ -1243,7 +1233,7 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
             SM2_T(1);
             comb_half_sm2_26(G0, s, ctab, cbits, 0);
             SM2_T(2);
-            while (__hip_atomic_load(&L.seq[2], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
+            while (__hip_atomic_load(&L.seq[kSeqCombHalf], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
                 __builtin_amdgcn_s_sleep(1);
             }
             pair26_load_jac(G1, L.gh, lane);
@@ -1254,8 +1244,8 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
         } else {
             // the affine table of all 40 txs (one lane per tx) from the Jacobian entries (waves 2 and 3):
             // one inversion of Z1 .. Z7, then x = X / Z^2, y = Y / Z^3; the chains switch to it when ready
-            while (__hip_atomic_load(&L.seq[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u ||
-                   __hip_atomic_load(&L.seq[1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
+            while (__hip_atomic_load(&L.seq[kSeqJacTab0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u ||
+                   __hip_atomic_load(&L.seq[kSeqJacTab1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
                 __builtin_amdgcn_s_sleep(1);
             }
             {
@@ -1301,13 +1291,13 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
                 });
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane == 0) __hip_atomic_store(&L.seq[3], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0) __hip_atomic_store(&L.seq[kSeqAffineTab], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             JacP26 G1;
             SM2_T(1);
             comb_half_sm2_26(G1, s, ctab, cbits, 1);
             SM2_T(2);
             pair26_store_jac(L.gh, G1, lane);
-            __hip_atomic_store(&L.seq[2], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store(&L.seq[kSeqCombHalf], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         if constexpr (split > 0) {
             // the low windows of txs 0..19 (wave 2) / 20..39 (wave 3), from ONE call site: inlined into each
@@ -1318,9 +1308,9 @@ __global__ __launch_bounds__(256, 1) void tx_verify_sm2_trio26_kernel(IO io, uin
             SM2_T(7);
             if (wave == 3) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (lane == 0) __hip_atomic_store(&L.seq[4], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (lane == 0) __hip_atomic_store(&L.seq[kSeqLowSum], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             } else {  // s G + the low sums for all 40 txs
-                while (__hip_atomic_load(&L.seq[4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
+                while (__hip_atomic_load(&L.seq[kSeqLowSum], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {
                     __builtin_amdgcn_s_sleep(1);
                 }
                 lds_wave_sync();

@@ -40,12 +40,6 @@ struct RowLds {
     InvQueue invq;                // phase D: Z^-1 split over waves 0 (divsteps, f, g) and 1 (d, e)
 };
 
-__device__ __forceinline__ void row_post(uint32_t* f) {
-    __hip_atomic_store(f, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void row_wait(uint32_t* f) {
-    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) __builtin_amdgcn_s_sleep(1);
-}
 __device__ __forceinline__ void put8(uint32_t* d, const fe& a, int lane) {
     if (lane < 8) d[lane] = a.v[lane];
 }
@@ -173,7 +167,7 @@ __global__ __launch_bounds__(256, 1) void recover_row_kernel(IO io, uint64_t n, 
         fe rm, rinv;
         FieldN1::from_plain(rm, inv_of);
         FieldInv<FieldN1>::inv_var(rinv, rm);  // variable time: every lane holds the same value
-        row_wait(&S.post[0]);
+        lds_flag_wait(&S.post[0]);
         fe e, u1, u2, k1, k2;
         get8(e, S.e);
         FieldN1::mul(u1, e, rinv);
@@ -187,19 +181,19 @@ __global__ __launch_bounds__(256, 1) void recover_row_kernel(IO io, uint64_t n, 
             S.k[1][lane] = k2.v[lane];
         }
         if (lane == 0) S.kflags = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
-        row_post(&S.post[1]);
+        lds_flag_post(&S.post[1]);
     } else {
         if (wave == 1) {
             fe e;
             io.template digest<KECCAK256>(i, e);
             reduce_once(e, ParamN1::M);
             put8(S.e, e, lane);
-            row_post(&S.post[0]);
+            lds_flag_post(&S.post[0]);
         }
         if constexpr (kVer) {
             if (wave == 3) {  // the chains map to E with Z Zc alone
-                row_wait(&S.post[2]);
-                row_wait(&S.post[3]);
+                lds_flag_wait(&S.post[2]);
+                lds_flag_wait(&S.post[3]);
                 if (L.row == 0) {
                     S.zcy[0][L.k] = S.zc[0][L.k];
                     S.zcy[1][L.k] = S.zc[1][L.k];
@@ -227,7 +221,7 @@ __global__ __launch_bounds__(256, 1) void recover_row_kernel(IO io, uint64_t n, 
                 fe26 beta26;
                 fe26_const(beta26, kGlvBeta);
                 frow::build_table(S.tab[wave - 1], S.zc[wave - 1], P, frow::from_fe26(beta26, L), fk);
-                row_post(&S.post[wave == 1 ? 2 : 3]);
+                lds_flag_post(&S.post[wave == 1 ? 2 : 3]);
             }
         } else {
         // x = r (+ n), w = x^3 + 7 and R' = (w x, w^2) on E_w: Y^2 = X^3 + 7 w^3 (a point (X, Y, Z) of E_w
@@ -255,8 +249,8 @@ __global__ __launch_bounds__(256, 1) void recover_row_kernel(IO io, uint64_t n, 
             fe26_cmov(y, ny, (y.v[0] & 1u) != (v & 1u));
             const uint32_t yr = frow::from_fe26(y, L);
             if (lane == 0) S.rflag = okr ? 2u : 0u;
-            row_wait(&S.post[2]);
-            row_wait(&S.post[3]);
+            lds_flag_wait(&S.post[2]);
+            lds_flag_wait(&S.post[3]);
             uint32_t a, b;
             frow::gather01(frow::mul(frow::sel4(L, S.zc[0][L.k], S.zc[1][L.k], S.zc[1][L.k], S.zc[1][L.k]), yr, L), a,
                            b);
@@ -275,16 +269,16 @@ __global__ __launch_bounds__(256, 1) void recover_row_kernel(IO io, uint64_t n, 
             fe26 beta26;
             fe26_const(beta26, kGlvBeta);
             frow::build_table(S.tab[wave - 1], S.zc[wave - 1], P, frow::from_fe26(beta26, L), fk);
-            row_post(&S.post[wave == 1 ? 2 : 3]);
+            lds_flag_post(&S.post[wave == 1 ? 2 : 3]);
         }
         }
     }
     ROW_T(1);
     // ---------------------------------------------------------------- phase C: four 64-bit GLV chains
     // wave 0: low half of k1 on R', 1: low half of k2 on phi(R'), 2 / 3: the high halves on 2^64 R'
-    row_wait(&S.post[1]);
-    row_wait(&S.post[2]);
-    row_wait(&S.post[3]);
+    lds_flag_wait(&S.post[1]);
+    lds_flag_wait(&S.post[2]);
+    lds_flag_wait(&S.post[3]);
     {
         const int kh = wave & 1, part = wave >> 1;
         fe k;
@@ -593,9 +587,9 @@ __global__ __launch_bounds__(256, 1) void sm2_verify_row_kernel(IO io, uint64_t 
         frow::pt_store(S.pt[wave - 1], g, L);
         if (lane == 0) S.pinf[wave - 1] = ginf ? 1u : 0u;
         if (wave == 3) {
-            row_post(&S.post[2]);
+            lds_flag_post(&S.post[2]);
         } else {  // wave 2: the two halves
-            row_wait(&S.post[2]);
+            lds_flag_wait(&S.post[2]);
             frow::Pt Q, R;
             bool rinf;
             frow::pt_load(Q, S.pt[2], L);

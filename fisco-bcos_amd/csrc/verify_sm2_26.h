@@ -167,10 +167,7 @@ __device__ __forceinline__ void booth_mul_sm2_26(JacP26& acc, const fe& k_plain,
         CurveSM2x::dbl(acc, acc);
         CurveSM2x::dbl(acc, acc);
         CurveSM2x::dbl(acc, acc);
-        const uint32_t top = k.v[7];
-        const uint32_t W = top >> 28, c = (top >> 27) & 1u;
-        const int d = static_cast<int>(W + c) - static_cast<int>((W >> 3) << 4);
-        shl4(k);
+        const int d = booth_digit256(k);
         add_digit_sm2_26<LDS>(acc, ldsx, X, Y, d);
     }
 }
