@@ -577,8 +577,7 @@ int bcosgpu_register_keys(int device, int suite, const uint8_t* pub64, size_t n,
     if (int rc = ready_device(device)) return rc;
     DeviceScope on(device);
     if (on.err != hipSuccess) return set_err(BCOSGPU_E_HIP, "hipSetDevice failed");
-    bool all = false;
-    if (int rc = keyed_slots(suite, pub64, 64, n, slots, true, &all, nullptr)) return set_err(rc, "key table build failed");
+    if (int rc = keyed_register(suite, pub64, n, slots)) return set_err(rc, "key table build failed");
     int cached = 0;
     for (size_t i = 0; i < n; ++i) cached += slots[i] >= 0;
     return cached;

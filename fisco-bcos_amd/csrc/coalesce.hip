@@ -250,8 +250,8 @@ int run_batch(int device, int kind, Slot& slot, std::vector<SigJob*>& batch, std
         // (admission: the key is the sender's, embedded in the signature) only looks them up
         bool named = true;
         for (SigJob* j : batch) named = named && (kind == kSigJobVerifyK1 || j->pub64 != nullptr);
-        const int krc = keyed_slots(vsuite, pubs, kind == kSigJobVerifySM2 ? 128 : 64, n,
-                                    reinterpret_cast<int32_t*>(in + slots_at), false, &keyed, slot.stream, &gen, named);
+        const int krc = keyed_lookup(vsuite, pubs, kind == kSigJobVerifySM2 ? 128 : 64, n,
+                                     reinterpret_cast<int32_t*>(in + slots_at), named, &keyed, &gen);
         if (krc) keyed = false;  // a failed table build leaves the generic path
     }
     // the slot goes back to the queue with its stream idle, whatever way the batch ends

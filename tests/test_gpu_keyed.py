@@ -104,7 +104,7 @@ def _oracle_verify(oracle, suite, pub, h, sig):
 
 
 def _wait_built(gpu, suite, target, timeout=10.0):
-    """Promotion builds run asynchronously (ecc_keyed.hip keyed_slots): poll the cache until `target` tables
+    """Promotion builds run asynchronously (ecc_keyed.hip keyed_lookup): poll the cache until `target` tables
     have been built and published."""
     import time
     t0 = time.monotonic()
@@ -324,7 +324,7 @@ def test_promotion_counts_calls_not_occurrences(gpu, oracle):
 
 
 def test_promotion_under_concurrent_calls(gpu, oracle):
-    """Promotion builds run asynchronously (ecc_keyed.hip keyed_slots: one build in flight, published when
+    """Promotion builds run asynchronously (ecc_keyed.hip keyed_lookup: one build in flight, published when
     its event completes): 24 threads make single SignatureCrypto::verify calls over 48 keys -- each key
     seen many times, so builds start, complete and publish while other threads look the same keys up --
     and a registration of half the keys (which waits for a build in flight) lands in the middle.  Every verdict equals the expected one (1 in 4 signatures corrupted), every
@@ -374,3 +374,73 @@ def test_promotion_under_concurrent_calls(gpu, oracle):
         assert np.array_equal(_keyed_dev(suite, slots, h[::2], sig[::2]), want[::2])
         assert np.array_equal(crypto.verify_batch(pub, h, sig), want)
         gpu.clear_keys(suite)
+
+
+def _invalid_keys_and_spare_rows(gpu, oracle):
+    """Per suite: three registered keys -- valid, off the curve, x >= p (the last two get G's multiples and
+    valid = 0 from the table kernel's one body) -- and 4 + 1 signatures, so the second workgroup has three
+    spare rows that re-run the last signature and must store nothing: two guard bytes behind `ok` stay."""
+    import torch
+    from bcos_gpu import device
+    rng = np.random.default_rng(31)
+    for suite in (0, 1):
+        sk = _keys(rng, 3)
+        pub, _, ok = _dev_sign(gpu, suite, sk, np.zeros((3, 32), dtype=np.uint8))
+        assert ok.all()
+        pub = pub.copy()
+        pub[1, 63] ^= 1      # off the curve
+        pub[2, 0:32] = 0xFF  # x >= p
+        slots = gpu.register_keys(suite, pub)
+        assert (slots >= 0).all() and len(set(slots.tolist())) == 3
+        who = np.array([0, 1, 2, 0, 0])
+        h = rng.integers(0, 256, size=(5, 32), dtype=np.uint8)
+        _, sig, ok = _dev_sign(gpu, suite, sk[who], h)
+        assert ok.all()
+        sig = sig.copy()
+        sig[3, 40] ^= 2  # the valid key, a corrupted s; the last signature (the spare rows') is valid
+        want = [_oracle_verify(oracle, suite, pub[k].tobytes(), h[i].tobytes(), sig[i].tobytes())
+                for i, k in enumerate(who)]
+        assert want == [True, False, False, False, True]
+        d_slots = torch.from_numpy(slots[who].astype(np.int32)).cuda()
+        d_h = torch.from_numpy(h).cuda()
+        d_s = torch.from_numpy(np.ascontiguousarray(sig)).cuda()
+        d_ok = torch.full((7,), 0xA5, dtype=torch.uint8, device="cuda")
+        device.verify_keyed(suite, d_slots, d_h, d_s, d_ok[:5])
+        torch.cuda.synchronize()
+        got = d_ok.cpu().numpy()
+        assert got[:5].astype(bool).tolist() == want and got[:5].max() <= 1, (suite, got)
+        assert got[5] == 0xA5 and got[6] == 0xA5, (suite, got)
+        gpu.clear_keys(suite)
+
+
+_SMALL_TABLES_KEYED_SCRIPT = """
+import sys
+sys.path[:0] = [{pkg!r}, {root!r}, {tests!r}]
+import bcos_gpu
+from oracle import oracle
+import test_gpu_keyed
+oracle.build()
+bcos_gpu.check(bcos_gpu.lib().bcosgpu_init_ex(0, 1))  # BCOSGPU_INIT_SMALL_TABLES
+test_gpu_keyed._invalid_keys_and_spare_rows(bcos_gpu, oracle)
+print("small-tables keyed ok")
+"""
+
+
+def test_invalid_keys_and_spare_rows(gpu, oracle):
+    """The table kernel's invalid-key branch and the verify kernel's spare rows, both suites, on G's 16-bit
+    comb (the default tables)."""
+    _invalid_keys_and_spare_rows(gpu, oracle)
+
+
+def test_invalid_keys_and_spare_rows_small_tables():
+    """The same with bcosgpu_init_ex(dev, BCOSGPU_INIT_SMALL_TABLES): a lane adds windows 2L, 2L+1 of G's 8-bit
+    comb (the other branch of keyed_row_sum).  Own process: the flag only matters at a device's first
+    initialisation."""
+    import os
+    import subprocess
+    import sys
+    tests = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(tests)
+    code = _SMALL_TABLES_KEYED_SCRIPT.format(pkg=os.path.join(root, "fisco-bcos_amd"), root=root, tests=tests)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "small-tables keyed ok" in r.stdout, (r.stdout[-1000:], r.stderr[-2000:])
