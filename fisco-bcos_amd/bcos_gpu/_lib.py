@@ -83,6 +83,12 @@ _SIGS = {
     "bcosgpu_state_root_work_size": (ctypes.c_uint64, [_SZ]),
     "bcosgpu_state_root_dev": (_I, [_I, ctypes.c_uint32, _P, _P, _P, _SZ, _P, ctypes.c_uint64, _P, _P]),
     "bcosgpu_state_root": (_I, [_I, ctypes.c_uint32, _P, _SZ, _P]),
+    "bcosgpu_header_preimage_size": (ctypes.c_uint64, [_P, _SZ, _I]),
+    "bcosgpu_pack_header_preimages": (_I, [_P, _SZ, _I, _P, ctypes.c_uint64, _P]),
+    "bcosgpu_headers_check_work_size": (ctypes.c_uint64, [_SZ, _SZ]),
+    "bcosgpu_headers_check_dev": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P,
+                                       ctypes.c_uint64, _SZ, _SZ, _P, _P, _P, _P, _P, ctypes.c_uint64, _P]),
+    "bcosgpu_headers_check": (_I, [_I, _P, _SZ, _P, _P, ctypes.c_int64, _I, _P, _P, _P, _P]),
     "bcosgpu_tars_decode_work_size": (ctypes.c_uint64, [_SZ]),
     "bcosgpu_tars_tx_decode_dev": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P, ctypes.c_uint64, _P]),
     "bcosgpu_tars_tx_verify_batch": (_I, [_I, _P, _P, _SZ, _I, _I, _P, _P, _P]),

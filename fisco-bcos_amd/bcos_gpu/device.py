@@ -50,6 +50,29 @@ def state_root(hasher, block_version, data, off3, kind, work, root, stream=None)
                                        work.numel() * work.element_size(), _p(root), _s(stream)))
 
 
+def headers_check_work_size(n, rows):
+    return int(lib().bcosgpu_headers_check_work_size(n, rows))
+
+
+def headers_check(suite, pre, pre_off, pre_status, number, parent_number, parent_hash, parent_ok, sig_off, sig,
+                  row_weight, quorum, hashes, check_out, link, work, given=None, given_mask=None, prev_hash=None,
+                  prev_number=0, row_slot=None, row_pub=None, sig_ok=None, stream=None):
+    """The block-header check of n headers over `rows` signature rows (bcosgpu_headers_check_dev): pre uint8[B],
+    pre_off int64[n+1], pre_status uint8[n], number / parent_number int64[n], parent_hash uint8[n,32], parent_ok
+    uint8[n], sig_off int64[n+1], sig uint8[rows,64], row_weight int64[rows] (read as u64), exactly one of
+    row_slot int32[rows] / row_pub uint8[rows,64]; given uint8[n,32] with given_mask uint8[n], prev_hash
+    uint8[32] and sig_ok uint8[rows] may be None -> hashes uint8[n,32], check_out uint8[n], link uint8[n]."""
+    _dev(hashes)
+    n = pre_off.numel() - 1
+    rows = row_weight.numel()
+    check(lib().bcosgpu_headers_check_dev(suite, _p(pre), _p(pre_off), _p(given), _p(given_mask), _p(pre_status),
+                                          _p(number), _p(parent_number), _p(parent_hash), _p(parent_ok),
+                                          _p(prev_hash), prev_number, _p(sig_off), _p(sig), _p(row_weight),
+                                          _p(row_slot), _p(row_pub), quorum, n, rows, _p(hashes), _p(check_out),
+                                          _p(link), _p(sig_ok), _p(work), work.numel() * work.element_size(),
+                                          _s(stream)))
+
+
 def merkle_size(n, width):
     return int(lib().bcosgpu_merkle_size(n, width))
 

@@ -426,6 +426,208 @@ int bcosgpu_state_root(int hasher, uint32_t block_version, const bcosgpu_StateEn
     return c.finish();
 }
 
+// ------------------------------------------------------------------ block headers (header_kernels.hip)
+uint64_t bcosgpu_headers_check_work_size(size_t n, size_t rows) { return headers_check_work_bytes(n, rows); }
+
+int bcosgpu_headers_check_dev(int suite, const uint8_t* d_pre, const uint64_t* d_pre_off, const uint8_t* d_given32,
+                              const uint8_t* d_given_mask, const uint8_t* d_pre_status, const int64_t* d_number,
+                              const int64_t* d_parent_number, const uint8_t* d_parent_hash32,
+                              const uint8_t* d_parent_ok, const uint8_t* d_prev_hash32, int64_t prev_number,
+                              const uint64_t* d_sig_off, const uint8_t* d_sig, const uint64_t* d_row_weight,
+                              const int32_t* d_row_slot, const uint8_t* d_row_pub64, uint64_t quorum, size_t n,
+                              size_t rows, uint8_t* d_hash32, uint8_t* d_check, uint8_t* d_link, uint8_t* d_sig_ok,
+                              void* d_work, uint64_t work_bytes, void* stream) {
+    if (int rc = check_suite(suite)) return rc;
+    if (n == 0) return 0;
+    if (!d_pre || !d_pre_off || !d_pre_status || !d_number || !d_parent_number || !d_parent_hash32 || !d_parent_ok ||
+        !d_sig_off || !d_hash32 || !d_check || !d_link || !d_work || (rows && (!d_sig || !d_row_weight)))
+        return set_err(BCOSGPU_E_ARG, "null pointer");
+    if (rows && (d_row_slot != nullptr) == (d_row_pub64 != nullptr))
+        return set_err(BCOSGPU_E_ARG, "exactly one of d_row_slot and d_row_pub64 must be given");
+    HeadersCheckArgs a;
+    a.d_pre = d_pre, a.d_pre_off = d_pre_off, a.d_given32 = d_given32, a.d_given_mask = d_given_mask;
+    a.d_pre_status = d_pre_status, a.d_number = d_number, a.d_parent_number = d_parent_number;
+    a.d_parent_hash32 = d_parent_hash32, a.d_parent_ok = d_parent_ok, a.d_prev_hash32 = d_prev_hash32;
+    a.prev_number = prev_number, a.d_sig_off = d_sig_off, a.d_sig = d_sig, a.d_row_weight = d_row_weight;
+    a.d_row_slot = d_row_slot, a.d_row_pub64 = d_row_pub64, a.quorum = quorum, a.n = n, a.rows = rows;
+    a.d_hash32 = d_hash32, a.d_check = d_check, a.d_link = d_link, a.d_sig_ok = d_sig_ok;
+    a.d_work = d_work, a.work_bytes = work_bytes;
+    const int rc = launch_headers_check(suite, a, as_stream(stream));
+    if (rc == BCOSGPU_E_ARG)
+        return set_err(rc, "work buffer too small, batch too large, or no key registered on this device");
+    return rc ? hip_err(hipGetLastError(), "headers check launch") : 0;
+}
+
+// The host-side part of asyncCheckBlock for one header (BlockValidator.cpp:35-63 with
+// checkSealerListAndWeightList, :80-139): the early verdict, 0 = go on to the signature rows.
+static uint8_t header_pre_status(const bcosgpu_BlockHeaderData& h, const bcosgpu_ConsensusSet& cs) {
+    if (h.block_number == 0) return BCOSGPU_HEADER_GENESIS;                         // :35-39
+    if (h.block_number <= cs.committed_index) return BCOSGPU_HEADER_E_COMMITTED;    // :49-53
+    if (h.tx_count == 0) return BCOSGPU_HEADER_NO_TXS;                              // :54-58
+    if (h.sealer < 0 || static_cast<uint64_t>(h.sealer) >= cs.n) return BCOSGPU_HEADER_E_SEALER;  // :85-93
+    if (h.nsealer_list != cs.n || h.nconsensus_weights != cs.n) return BCOSGPU_HEADER_E_SEALER_LIST;  // :98-108
+    for (size_t k = 0; k < cs.n; ++k) {                                             // :110-137
+        const bcosgpu_Bytes& id = h.sealer_list[k];
+        if (id.len != 64 || std::memcmp(id.data, cs.node_ids64 + 64 * k, 64) != 0) return BCOSGPU_HEADER_E_SEALER_LIST;
+        if (static_cast<uint64_t>(h.consensus_weights[k]) != cs.weights[k]) return BCOSGPU_HEADER_E_SEALER_LIST;
+    }
+    return 0;
+}
+
+// BlockValidator::asyncCheckBlock and the ledger's parent check for a run of headers (see bcos_gpu.h): the
+// early verdicts and the rows' keys and weights on the host, everything packed into pinned staging as one
+// block (64-bit arrays first, the preimages last), one H2D, the three phases, one D2H.
+int bcosgpu_headers_check(int suite, const bcosgpu_BlockHeaderData* headers, size_t n,
+                          const bcosgpu_ConsensusSet* consensus, const uint8_t* prev_hash32_or_null,
+                          int64_t prev_number, int flags, uint8_t* hash32, uint8_t* check, uint8_t* link,
+                          uint8_t* sig_ok_or_null) {
+    if (int rc = check_suite(suite)) return rc;
+    if (n == 0) return 0;
+    if (!headers || !consensus || !hash32 || !check || !link) return set_err(BCOSGPU_E_ARG, "null pointer");
+    const bcosgpu_ConsensusSet& cs = *consensus;
+    if (cs.n && (!cs.node_ids64 || !cs.weights)) return set_err(BCOSGPU_E_ARG, "null consensus set");
+    if (cs.n > 0x7FFFFFFFull) return set_err(BCOSGPU_E_ARG, "consensus set too large");
+    // bad views first (the packer checks the hashed fields again; it does not see the signatures)
+    for (size_t i = 0; i < n; ++i) {
+        const bcosgpu_BlockHeaderData& h = headers[i];
+        if ((!h.signatures && h.nsignatures) || (!h.sealer_list && h.nsealer_list) ||
+            (!h.consensus_weights && h.nconsensus_weights) || (!h.parents && h.nparents) ||
+            (h.data_hash_len && (!h.data_hash || h.data_hash_len > 32)))
+            return set_err(BCOSGPU_E_ARG, "bad header view (null field with a length, or a dataHash over 32 bytes)");
+        for (size_t k = 0; k < h.nsealer_list; ++k)
+            if (!h.sealer_list[k].data && h.sealer_list[k].len) return set_err(BCOSGPU_E_ARG, "bad header view");
+        for (size_t s = 0; s < h.nsignatures; ++s)
+            if (!h.signatures[s].signature && h.signatures[s].signature_len)
+                return set_err(BCOSGPU_E_ARG, "bad header view (null signature with a length)");
+    }
+    std::vector<uint8_t> pre_status(n);
+    uint64_t rows = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (!(pre_status[i] = header_pre_status(headers[i], cs))) rows += headers[i].nsignatures;
+    WsCall c;
+    if (c.rc) return c.rc;
+    Workspace* w = c.w;
+    // the consensus keys' slot ids; ids for all of them, or the rows carry the keys
+    std::vector<int32_t> slots(cs.n, -1);
+    const uint64_t gen = keyed_generation(suite);
+    bool keyed = rows != 0;
+    if (keyed) {
+        if (keyed_register(suite, cs.node_ids64, cs.n, slots.data())) {
+            (void)hipGetLastError();  // a failed table build leaves the key path
+            keyed = false;
+        }
+        for (size_t k = 0; keyed && k < cs.n; ++k) keyed = slots[k] >= 0;
+    }
+    const uint64_t pre_bytes = bcosgpu_header_preimage_size(headers, n, flags);
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 7) & ~uint64_t{7};
+        return o;
+    };
+    const uint64_t o_pre_off = take(8 * (n + 1)), o_sig_off = take(8 * (n + 1)), o_number = take(8 * n),
+                   o_pnum = take(8 * n), o_weight = take(8 * rows), o_phash = take(32 * n), o_given = take(32 * n),
+                   o_prev = take(32), o_sig = take(64 * rows), o_key = take(keyed ? 4 * rows : 64 * rows),
+                   o_mask = take(n), o_status = take(n), o_pok = take(n), o_pre = take(pre_bytes);
+    const uint64_t total = at;
+    HIP_OK(w->h[0].ensure(total + 16));
+    uint8_t* hs = w->h[0].as<uint8_t>();
+    uint64_t* pre_off = reinterpret_cast<uint64_t*>(hs + o_pre_off);
+    if (bcosgpu_pack_header_preimages(headers, n, flags, hs + o_pre, pre_bytes, pre_off))
+        return set_err(BCOSGPU_E_ARG, "bad header view (null field with a length, a dataHash over 32 bytes, or a header "
+                                      "of 4 GiB or more)");
+    uint64_t* sig_off = reinterpret_cast<uint64_t*>(hs + o_sig_off);
+    int64_t* number = reinterpret_cast<int64_t*>(hs + o_number);
+    int64_t* pnum = reinterpret_cast<int64_t*>(hs + o_pnum);
+    uint64_t* weight = reinterpret_cast<uint64_t*>(hs + o_weight);
+    int32_t* row_slot = reinterpret_cast<int32_t*>(hs + o_key);
+    std::vector<int32_t> row_node(rows);  // the consensus node of each row, -1 = the row fails without a key
+    std::memset(hs + o_phash, 0, 64 * n);  // parent hashes, given hashes
+    std::memset(hs + o_sig, 0, 64 * rows);
+    if (!keyed) std::memset(hs + o_key, 0, 64 * rows);
+    if (prev_hash32_or_null) std::memcpy(hs + o_prev, prev_hash32_or_null, 32);
+    uint64_t r = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bcosgpu_BlockHeaderData& h = headers[i];
+        number[i] = h.block_number;
+        const bool pok = h.nparents && h.parents[0].block_hash_len == 32;  // LedgerImpl.h:302-306 reads [0] only
+        pnum[i] = h.nparents ? h.parents[0].block_number : 0;
+        hs[o_pok + i] = pok;
+        if (pok) std::memcpy(hs + o_phash + 32 * i, h.parents[0].block_hash, 32);
+        const bool given = h.data_hash_len && !(flags & BCOSGPU_HEADER_RECOMPUTE);  // TarsHashable.h:81-85
+        hs[o_mask + i] = given;
+        if (given) std::memcpy(hs + o_given + 32 * i, h.data_hash, h.data_hash_len);
+        hs[o_status + i] = pre_status[i];
+        sig_off[i] = r;
+        if (pre_status[i]) continue;
+        for (size_t s = 0; s < h.nsignatures; ++s, ++r) {
+            const bcosgpu_HeaderSignature& sg = h.signatures[s];
+            // no such node (ConsensusConfig.cpp:150-158), or shorter than verify accepts (bcos_gpu.hpp:94-115)
+            const bool ok = sg.sealer_index >= 0 && static_cast<uint64_t>(sg.sealer_index) < cs.n && sg.signature_len >= 64;
+            const int32_t node = ok ? static_cast<int32_t>(sg.sealer_index) : -1;
+            row_node[r] = node;
+            weight[r] = ok ? cs.weights[node] : 0;
+            if (ok) std::memcpy(hs + o_sig + 64 * r, sg.signature, 64);
+            if (keyed) row_slot[r] = ok ? slots[node] : -1;
+            else if (ok) std::memcpy(hs + o_key + 64 * r, cs.node_ids64 + 64 * node, 64);
+        }
+    }
+    sig_off[n] = r;
+    const uint64_t work = headers_check_work_bytes(n, rows);
+    const uint64_t out_ok = (34 * n + 7) & ~uint64_t{7}, out_bytes = out_ok + rows;
+    HIP_OK(w->h[1].ensure(out_bytes + 16));
+    HIP_OK(c.ensure({total + 16, work, out_bytes + 16}));
+    HIP_OK(c.h2d(0, hs, total));
+    const uint8_t* di = c.buf(0);
+    uint8_t* dout = c.buf(2);
+    uint8_t* ho = w->h[1].as<uint8_t>();
+    HeadersCheckArgs a;
+    a.d_pre = di + o_pre, a.d_pre_off = reinterpret_cast<const uint64_t*>(di + o_pre_off);
+    a.d_given32 = di + o_given, a.d_given_mask = di + o_mask, a.d_pre_status = di + o_status;
+    a.d_number = reinterpret_cast<const int64_t*>(di + o_number);
+    a.d_parent_number = reinterpret_cast<const int64_t*>(di + o_pnum);
+    a.d_parent_hash32 = di + o_phash, a.d_parent_ok = di + o_pok;
+    a.d_prev_hash32 = prev_hash32_or_null ? di + o_prev : nullptr, a.prev_number = prev_number;
+    a.d_sig_off = reinterpret_cast<const uint64_t*>(di + o_sig_off), a.d_sig = di + o_sig;
+    a.d_row_weight = reinterpret_cast<const uint64_t*>(di + o_weight);
+    if (keyed) a.d_row_slot = reinterpret_cast<const int32_t*>(di + o_key);
+    else a.d_row_pub64 = di + o_key;
+    a.quorum = cs.min_required_quorum, a.n = n, a.rows = rows;
+    a.d_hash32 = dout, a.d_check = dout + 32 * n, a.d_link = dout + 33 * n, a.d_sig_ok = dout + out_ok;
+    a.d_work = c.buf<void>(1), a.work_bytes = work;
+    std::vector<uint8_t> pubs;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const int rc = launch_headers_check(suite, a, c.stream());
+        if (rc == BCOSGPU_E_ARG) return set_err(rc, "batch too large");
+        if (rc) return hip_err(hipGetLastError(), "headers check launch");
+        HIP_OK(hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, c.stream()));
+        HIP_OK(hipStreamSynchronize(c.stream()));
+        // the key cache was cleared (bcosgpu_clear_keys) between the registration and here: the ids may name
+        // other keys' tables by now, so the run is repeated with the keys in the rows (as coalesce.hip does)
+        if (!a.d_row_slot || keyed_generation(suite) == gen) break;
+        pubs.assign(64 * rows, 0);
+        for (uint64_t q = 0; q < rows; ++q)
+            if (row_node[q] >= 0) std::memcpy(pubs.data() + 64 * q, cs.node_ids64 + 64 * row_node[q], 64);
+        HIP_OK(w->b[3].ensure(64 * rows));
+        HIP_OK(c.h2d(3, pubs.data(), 64 * rows));
+        a.d_row_slot = nullptr, a.d_row_pub64 = c.buf(3);
+    }
+    if (int rc = c.finish()) return rc;
+    std::memcpy(hash32, ho, 32 * n);
+    std::memcpy(check, ho + 32 * n, n);
+    std::memcpy(link, ho + 33 * n, n);
+    if (sig_ok_or_null) {  // rows -> one entry per signature; 2 = the header's signatures were not checked
+        uint64_t s = 0, q = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t m = headers[i].nsignatures;
+            if (pre_status[i]) std::memset(sig_ok_or_null + s, 2, m);
+            else if (m) std::memcpy(sig_ok_or_null + s, ho + out_ok + q, m), q += m;
+            s += m;
+        }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ Merkle proofs
 uint64_t bcosgpu_merkle_proof_stride(uint64_t n, int width) {
     if (width < 2 || width > 64 || n == 0) return 0;

@@ -114,6 +114,66 @@ bool state_entry_len(const bcosgpu_StateEntry& e, uint64_t* len) {
     return true;
 }
 
+// ---- block headers: impl_calculate<Hasher>(bcostars::BlockHeader), TarsHashable.h:77-126.  A header with a
+// dataHash is not hashed (:81-85), so its preimage is empty here -- unless the caller asks to recompute.
+bool header_given(const bcosgpu_BlockHeaderData& h, int flags) {
+    return h.data_hash_len && !(flags & BCOSGPU_HEADER_RECOMPUTE);
+}
+
+size_t header_len(const bcosgpu_BlockHeaderData& h, int flags) {
+    if (header_given(h, flags)) return 0;
+    size_t s = 4 + h.txs_root_len + h.receipt_root_len + h.state_root_len + 8 + h.gas_used_len + 8 + 8 +
+               h.extra_data_len + 8 * h.nconsensus_weights;
+    for (size_t p = 0; h.parents && p < h.nparents; ++p) s += 8 + h.parents[p].block_hash_len;
+    for (size_t k = 0; h.sealer_list && k < h.nsealer_list; ++k) s += h.sealer_list[k].len;
+    return s;
+}
+
+// (the dataHash is checked whether or not it is used: a view that is wrong without the flag is wrong with it)
+bool valid(const bcosgpu_BlockHeaderData& h) {
+    if (h.data_hash_len && (!h.data_hash || h.data_hash_len > 32)) return false;
+    if ((!h.parents && h.nparents) || (!h.txs_root && h.txs_root_len) || (!h.receipt_root && h.receipt_root_len) ||
+        (!h.state_root && h.state_root_len) || (!h.gas_used && h.gas_used_len) || (!h.sealer_list && h.nsealer_list) ||
+        (!h.extra_data && h.extra_data_len) || (!h.consensus_weights && h.nconsensus_weights))
+        return false;
+    for (size_t p = 0; p < h.nparents; ++p)
+        if (!h.parents[p].block_hash && h.parents[p].block_hash_len) return false;
+    for (size_t k = 0; k < h.nsealer_list; ++k)
+        if (!h.sealer_list[k].data && h.sealer_list[k].len) return false;
+    return true;
+}
+
+// be32(version) || per parent (be64(blockNumber) || blockHash) || txsRoot || receiptRoot || stateRoot ||
+// be64(blockNumber) || gasUsed || be64(timestamp) || be64(sealer) || sealerList entries || extraData ||
+// be64 of every weight                                                            (TarsHashable.h:90-125)
+void pack_header(const bcosgpu_BlockHeaderData& h, int flags, uint8_t* o) {
+    if (header_given(h, flags)) return;
+    uint8_t w[8];
+    be(w, static_cast<uint32_t>(h.version), 4);
+    o = put(o, w, 4);
+    for (size_t p = 0; p < h.nparents; ++p) {
+        be(w, static_cast<uint64_t>(h.parents[p].block_number), 8);
+        o = put(o, w, 8);
+        o = put(o, h.parents[p].block_hash, h.parents[p].block_hash_len);
+    }
+    o = put(o, h.txs_root, h.txs_root_len);
+    o = put(o, h.receipt_root, h.receipt_root_len);
+    o = put(o, h.state_root, h.state_root_len);
+    be(w, static_cast<uint64_t>(h.block_number), 8);
+    o = put(o, w, 8);
+    o = put(o, h.gas_used, h.gas_used_len);
+    be(w, static_cast<uint64_t>(h.timestamp), 8);
+    o = put(o, w, 8);
+    be(w, static_cast<uint64_t>(h.sealer), 8);
+    o = put(o, w, 8);
+    for (size_t k = 0; k < h.nsealer_list; ++k) o = put(o, h.sealer_list[k].data, h.sealer_list[k].len);
+    o = put(o, h.extra_data, h.extra_data_len);
+    for (size_t k = 0; k < h.nconsensus_weights; ++k) {
+        be(w, static_cast<uint64_t>(h.consensus_weights[k]), 8);
+        o = put(o, w, 8);
+    }
+}
+
 // items [0, n) packed by `pack(i, out + offsets[i])` on a pool of std::threads over contiguous ranges
 template <class F>
 void pack_parallel(size_t n, F&& pack) {
@@ -218,6 +278,32 @@ int bcosgpu_pack_state_entries(const bcosgpu_StateEntry* entries, size_t n, uint
         put(o, e.value, state_value_len(e));
         kind[i] = static_cast<uint8_t>(static_cast<uint8_t>(e.status) | (e.flags << 4));
     });
+    return BCOSGPU_OK;
+}
+
+uint64_t bcosgpu_header_preimage_size(const bcosgpu_BlockHeaderData* headers, size_t n, int flags) {
+    if (!headers) return 0;
+    uint64_t s = 0;
+    for (size_t i = 0; i < n; ++i) s += header_len(headers[i], flags);
+    return s;
+}
+
+int bcosgpu_pack_header_preimages(const bcosgpu_BlockHeaderData* headers, size_t n, int flags, uint8_t* out,
+                                  uint64_t cap, uint64_t* offsets) {
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return BCOSGPU_OK;
+    }
+    if (!headers || !offsets) return BCOSGPU_E_ARG;
+    offsets[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!valid(headers[i])) return BCOSGPU_E_ARG;
+        const uint64_t len = header_len(headers[i], flags);
+        if (len >> 32) return BCOSGPU_E_ARG;  // the kernel's reader takes a 32-bit length
+        offsets[i + 1] = offsets[i] + len;
+    }
+    if (offsets[n] > cap || (offsets[n] && !out)) return BCOSGPU_E_ARG;
+    pack_parallel(n, [&](size_t i) { pack_header(headers[i], flags, out + offsets[i]); });
     return BCOSGPU_OK;
 }
 

@@ -399,6 +399,125 @@ int bcosgpu_state_root_dev(int hasher, uint32_t block_version, const uint8_t* d_
 int bcosgpu_state_root(int hasher, uint32_t block_version, const bcosgpu_StateEntry* entries, size_t n,
                        uint8_t* root32);
 
+/* ---------------------------------------------------------------- block headers (hash, parent link, quorum) */
+/* The check a syncing node runs on every downloaded block, for a run of consecutive headers in one call:
+ *   the header hash    impl_calculate<Hasher>(bcostars::BlockHeader), bcos-tars-protocol/.../impl/TarsHashable.h:77-126
+ *   the block check    BlockValidator::asyncCheckBlock, bcos-pbft/bcos-pbft/pbft/engine/BlockValidator.cpp:28-182
+ *                      (caller: bcos-sync/bcos-sync/state/DownloadingQueue.cpp:407)
+ *   the parent link    the ledger's header sync loop, bcos-ledger/src/libledger/LedgerImpl.h:290-312
+ * Views of bcostars::ParentInfo / Signature / BlockHeader (bcos-tars-protocol/.../tars/Block.tars:6-35):
+ * pointers into the caller's decoded header, nothing is copied until packing. */
+typedef struct { int64_t block_number; const uint8_t* block_hash; size_t block_hash_len; } bcosgpu_ParentInfo;
+typedef struct { int64_t sealer_index; const uint8_t* signature; size_t signature_len; } bcosgpu_HeaderSignature;
+typedef struct {
+    int32_t version;
+    const bcosgpu_ParentInfo* parents;  size_t nparents;
+    /* the three roots are hashed as whatever bytes the vectors hold, of any length (TarsHashable.h:98-100) */
+    const uint8_t* txs_root;      size_t txs_root_len;
+    const uint8_t* receipt_root;  size_t receipt_root_len;
+    const uint8_t* state_root;    size_t state_root_len;
+    int64_t block_number;
+    const char* gas_used;         size_t gas_used_len;
+    int64_t timestamp;
+    int64_t sealer;
+    const bcosgpu_Bytes* sealer_list;  size_t nsealer_list;
+    const uint8_t* extra_data;    size_t extra_data_len;
+    const int64_t* consensus_weights;  size_t nconsensus_weights;
+    /* BlockHeader.dataHash: when non-empty it IS the header hash (TarsHashable.h:81-85) and the fields above
+     * are not hashed -- unless BCOSGPU_HEADER_RECOMPUTE.  Lengths as for a receipt's dataHash: more than 32
+     * bytes is BCOSGPU_E_ARG, a shorter one fills the leading bytes and the rest are zero. */
+    const uint8_t* data_hash;     size_t data_hash_len;
+    const bcosgpu_HeaderSignature* signatures;  size_t nsignatures;
+    uint64_t tx_count; /* Block::transactionsSize(), for the short cut at BlockValidator.cpp:54-58 */
+} bcosgpu_BlockHeaderData;
+/* The consensus set the headers are checked against (PBFTConfig): n nodes, node i's 64-byte id (its public key,
+ * X||Y) at node_ids64 + 64 i and its weight weights[i]; minRequiredQuorum(); committedProposal()->index(). */
+typedef struct {
+    const uint8_t* node_ids64;
+    const uint64_t* weights;
+    size_t n;
+    uint64_t min_required_quorum;
+    int64_t committed_index;
+} bcosgpu_ConsensusSet;
+/* flag: ignore every dataHash and hash the fields (a node that does not trust a peer's header) */
+#define BCOSGPU_HEADER_RECOMPUTE 1
+/* Total preimage bytes of n headers (0 for a header whose dataHash is used). */
+uint64_t bcosgpu_header_preimage_size(const bcosgpu_BlockHeaderData* headers, size_t n, int flags);
+/* Packs the header-hash preimages (TarsHashable.h:90-125: be32(version) || per parent (be64(blockNumber) ||
+ * blockHash) || txsRoot || receiptRoot || stateRoot || be64(blockNumber) || gasUsed || be64(timestamp) ||
+ * be64(sealer) || every sealerList entry || extraData || be64 of every consensus weight) back to back into out
+ * (cap bytes) and writes offsets[n+1]; a header whose dataHash is used gets an empty preimage.  Host only,
+ * multithreaded for large batches.  BCOSGPU_E_ARG if cap is too small, a pointer is null with a non-zero
+ * length or count, or a dataHash is longer than 32 bytes. */
+int bcosgpu_pack_header_preimages(const bcosgpu_BlockHeaderData* headers, size_t n, int flags, uint8_t* out,
+                                  uint64_t cap, uint64_t* offsets);
+/* Verdicts.  check[i] -- header i is accepted iff the code is < 16; precedence is the reference's order of
+ * returns (BlockValidator.cpp:35-69):
+ *    0 passed every check            1 genesis, nothing checked (:35-39)     2 no transactions, nothing checked (:54-58)
+ *   16 number <= committed index (:49-53)                17 the sealer is not a consensus node (:85-93)
+ *   18 sealer list or weight list differs from the consensus set (:98-137)
+ *   19 a signature row failed (:149-170)                 20 weight below the quorum (:173-180)
+ * Signature rows follow the reference even where that surprises: a row whose index names no consensus node
+ * (negative included) fails (getConsensusNodeByIndex, ConsensusConfig.cpp:150-158); ONE failed row fails the
+ * block even if the remaining weight reaches the quorum (19 before 20); an index that appears twice is counted
+ * twice (the reference sums per list entry and never deduplicates).
+ * link[i] -- 1 linked: parentInfo[0].blockNumber is the previous header's number and its hash the previous
+ * header's hash (LedgerImpl.h:302-306); 0 not linked (also: parentInfo empty, or its hash not 32 bytes long);
+ * 2 not checked: block number 0 (:290), or the first header with no previous hash given. */
+#define BCOSGPU_HEADER_OK 0
+#define BCOSGPU_HEADER_GENESIS 1
+#define BCOSGPU_HEADER_NO_TXS 2
+#define BCOSGPU_HEADER_E_COMMITTED 16
+#define BCOSGPU_HEADER_E_SEALER 17
+#define BCOSGPU_HEADER_E_SEALER_LIST 18
+#define BCOSGPU_HEADER_E_SIGNATURE 19
+#define BCOSGPU_HEADER_E_QUORUM 20
+#define BCOSGPU_LINK_BROKEN 0
+#define BCOSGPU_LINK_OK 1
+#define BCOSGPU_LINK_UNCHECKED 2
+/* Bytes of d_work (4-byte aligned) for bcosgpu_headers_check_dev over n headers with `rows` signature rows. */
+uint64_t bcosgpu_headers_check_work_size(size_t n, size_t rows);
+/* The device path, stream-ordered, three phases on the one stream: header_hash_kernel (one header per lane:
+ * the digest of preimage i = d_pre[d_pre_off[i] .. d_pre_off[i+1]), or d_given32 + 32 i where d_given_mask[i]
+ * is set, to d_hash32 and to each of the header's rows in d_work), the existing known-key verify kernels over
+ * the rows (the registered-key kernel when d_row_slot is given, the generic one when d_row_pub64 is: exactly
+ * one of the two), and header_verdict_kernel (one header per lane: folds its rows -- all ok, and the u64 sum of
+ * their weights against `quorum` -- merges d_pre_status and writes d_check and d_link).  The hasher follows the
+ * suite (Keccak-256 with secp256k1, SM3 with SM2).  All pointers are device pointers; hash arrays and d_work
+ * are 4-byte aligned, 64-bit arrays 8-byte aligned:
+ *   d_given32 [32 n], d_given_mask [n]   both nullable: the hash of a header that came with a dataHash
+ *   d_pre_status [n]                     the host's early verdict (a code above; 0 = go on to the rows)
+ *   d_number [n]                         the block numbers
+ *   d_parent_number [n], d_parent_hash32 [32 n], d_parent_ok [n]   parentInfo[0]; parent_ok = 0 when parentInfo
+ *                                        is empty or its hash is not 32 bytes long
+ *   d_prev_hash32 (nullable), prev_number   the header before the first one
+ *   d_sig_off [n + 1]                    CSR: header i's rows are [d_sig_off[i], d_sig_off[i+1]); d_sig_off[n] = rows
+ *   d_sig [64 rows]                      r || s of each row;  d_row_weight [rows] (u64)
+ *   d_row_slot [rows] (ids of bcosgpu_register_keys; a negative or stale id fails its row) or d_row_pub64 [64 rows]
+ * Outputs d_hash32 [32 n], d_check [n], d_link [n], d_sig_ok [rows] (nullable).  d_work's earlier contents
+ * do not matter.  n and every preimage length must be below 2^32. */
+int bcosgpu_headers_check_dev(int suite, const uint8_t* d_pre, const uint64_t* d_pre_off, const uint8_t* d_given32,
+                              const uint8_t* d_given_mask, const uint8_t* d_pre_status, const int64_t* d_number,
+                              const int64_t* d_parent_number, const uint8_t* d_parent_hash32,
+                              const uint8_t* d_parent_ok, const uint8_t* d_prev_hash32, int64_t prev_number,
+                              const uint64_t* d_sig_off, const uint8_t* d_sig, const uint64_t* d_row_weight,
+                              const int32_t* d_row_slot, const uint8_t* d_row_pub64, uint64_t quorum, size_t n,
+                              size_t rows, uint8_t* d_hash32, uint8_t* d_check, uint8_t* d_link, uint8_t* d_sig_ok,
+                              void* d_work, uint64_t work_bytes, void* stream);
+/* The same from host views, on the calling thread's device: the host-side parts of asyncCheckBlock per header
+ * (genesis, committed, tx_count == 0, sealer in range, sealer list and weight list equal to the consensus set),
+ * each signature's index mapped to the consensus key and weight, the consensus keys registered (a cached key is
+ * a lookup; when the cache cannot hold them all the rows carry the keys instead), everything packed into pinned
+ * staging, one H2D copy, the three phases, one D2H copy.  A header with a non-zero early verdict contributes no
+ * rows; it is still hashed and linked.  A signature shorter than 64 bytes, or one whose index names no
+ * consensus node, fails its row without a key.  hash32 [32 n], check [n], link [n]; sig_ok (nullable) has one
+ * entry per signature of every header, headers back to back: 1 verified, 0 failed, 2 not checked (the header
+ * had an early verdict).  Every row is verified, also those after a failed one.  n == 0 is a no-op. */
+int bcosgpu_headers_check(int suite, const bcosgpu_BlockHeaderData* headers, size_t n,
+                          const bcosgpu_ConsensusSet* consensus, const uint8_t* prev_hash32_or_null,
+                          int64_t prev_number, int flags, uint8_t* hash32, uint8_t* check, uint8_t* link,
+                          uint8_t* sig_ok_or_null);
+
 /* ---------------------------------------------------------------- single calls on an explicit device */
 /* One signature per call, for the reference's per-transaction call sites: TxPool's submitter threads
  * (TxPool.h:48-49) -> TxValidator::verify (TxValidator.cpp:56) -> Transaction::verify (Transaction.h:68-82)

@@ -266,6 +266,60 @@ inline HashType calculateStateRoot(const std::vector<bcosgpu_StateEntry>& entrie
     return root;
 }
 
+/* BlockHeader::hash -- impl_calculate<Hasher>(bcostars::BlockHeader) (TarsHashable.h:77-126) for a run of
+ * headers: the packed preimages through one hash call; a header's non-empty dataHash is its hash (:81-85,
+ * zero-filled to 32 bytes) unless flags has BCOSGPU_HEADER_RECOMPUTE. */
+template <int HASHER>
+inline std::vector<HashType> calculateBlockHeaderHash(const std::vector<bcosgpu_BlockHeaderData>& headers, int flags = 0) {
+    const size_t n = headers.size();
+    std::vector<HashType> out(n, HashType{});
+    if (n == 0) return out;
+    std::vector<uint64_t> off(n + 1, 0);
+    bytes pre(bcosgpu_header_preimage_size(headers.data(), n, flags) + 1);
+    if (bcosgpu_pack_header_preimages(headers.data(), n, flags, pre.data(), pre.size() - 1, off.data()) != BCOSGPU_OK)
+        throw std::invalid_argument("bcosgpu: bad block header view");
+    check(bcosgpu_hash_batch(HASHER, pre.data(), off.data(), n, out[0].data()));
+    for (size_t i = 0; i < n; ++i) {
+        const bcosgpu_BlockHeaderData& h = headers[i];
+        if (!h.data_hash_len || (flags & BCOSGPU_HEADER_RECOMPUTE)) continue;
+        out[i] = HashType{};
+        std::copy(h.data_hash, h.data_hash + h.data_hash_len, out[i].begin());
+    }
+    return out;
+}
+
+/* What checkBlockHeaders returns: per header its hash, the verdict of BlockValidator::asyncCheckBlock
+ * (BCOSGPU_HEADER_*; accepted iff < 16) and the parent link (BCOSGPU_LINK_*); per signature of every header,
+ * headers back to back, 1 verified / 0 failed / 2 not checked. */
+struct BlockHeaderCheck {
+    std::vector<HashType> hashes;
+    std::vector<uint8_t> check, link, sigOk;
+    bool accepted(size_t i) const { return check[i] < 16; }
+};
+
+/* The check a syncing node runs on every downloaded block (BlockValidator::asyncCheckBlock,
+ * BlockValidator.cpp:28-182, called from DownloadingQueue.cpp:407) plus the ledger's parent check
+ * (LedgerImpl.h:290-312) for a run of consecutive headers in one engine call.  SUITE: BCOSGPU_SUITE_*; prevHash:
+ * the hash of the header before the first one (null: the first link is reported as not checked). */
+template <int SUITE>
+inline BlockHeaderCheck checkBlockHeaders(const std::vector<bcosgpu_BlockHeaderData>& headers,
+                                          const bcosgpu_ConsensusSet& consensus, const HashType* prevHash = nullptr,
+                                          int64_t prevNumber = 0, int flags = 0) {
+    const size_t n = headers.size();
+    size_t nsig = 0;
+    for (const bcosgpu_BlockHeaderData& h : headers) nsig += h.nsignatures;
+    BlockHeaderCheck r;
+    r.hashes.assign(n, HashType{});
+    r.check.assign(n, 0);
+    r.link.assign(n, 0);
+    r.sigOk.assign(nsig, 0);
+    if (n == 0) return r;
+    check(bcosgpu_headers_check(SUITE, headers.data(), n, &consensus, prevHash ? prevHash->data() : nullptr, prevNumber,
+                                flags, r.hashes[0].data(), r.check.data(), r.link.data(),
+                                nsig ? r.sigOk.data() : nullptr));
+    return r;
+}
+
 /* EVM ecRecover precompile(bcos-executor/src/vm/Precompiled.cpp:443-482): {true, 32-byte output}
  * on success, {true, {}} on failure; `in` is read as 128 zero-padded bytes. */
 inline std::pair<bool, bytes> ecRecover(const uint8_t* in, size_t len) {
