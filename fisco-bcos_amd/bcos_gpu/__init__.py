@@ -9,6 +9,7 @@ from .crypto import (SM3, CryptoSuite, Hash, InvalidSignature, Keccak256, Merkle
                      secp256k1_suite, sm_suite)
 from . import tars
 from .header import (BlockHeader, ConsensusSet, HeaderSignature, check_headers, header_hashes, pack_headers)
+from .pbft import PBFTMessage, PrecommitProof, check_messages
 from .state import StateEntry, pack_state_entries, state_root
 from .tx import (LogEntry, Transaction, TransactionData, TransactionReceipt, TransactionReceiptData,
                  calculate_receipt_root, calculate_roots_batch, calculate_transaction_root, verify_packed,

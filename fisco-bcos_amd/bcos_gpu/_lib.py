@@ -89,6 +89,10 @@ _SIGS = {
     "bcosgpu_headers_check_dev": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P,
                                        ctypes.c_uint64, _SZ, _SZ, _P, _P, _P, _P, _P, ctypes.c_uint64, _P]),
     "bcosgpu_headers_check": (_I, [_I, _P, _SZ, _P, _P, ctypes.c_int64, _I, _P, _P, _P, _P]),
+    "bcosgpu_pbft_check_work_size": (ctypes.c_uint64, [_SZ, _SZ]),
+    "bcosgpu_pbft_check_dev": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _SZ,
+                                    ctypes.c_uint64, _SZ, _SZ, _P, _P, _P, _P, _P, ctypes.c_uint64, _P]),
+    "bcosgpu_pbft_check": (_I, [_I, _P, _SZ, _P, _SZ, _P, _I, _P, _P, _P, _P]),
     "bcosgpu_tars_decode_work_size": (ctypes.c_uint64, [_SZ]),
     "bcosgpu_tars_tx_decode_dev": (_I, [_P, _P, _SZ, _P, _P, _P, _P, _P, _P, ctypes.c_uint64, _P]),
     "bcosgpu_tars_tx_verify_batch": (_I, [_I, _P, _P, _SZ, _I, _I, _P, _P, _P]),

@@ -73,6 +73,32 @@ def headers_check(suite, pre, pre_off, pre_status, number, parent_number, parent
                                           _s(stream)))
 
 
+def pbft_check_work_size(n, rows):
+    return int(lib().bcosgpu_pbft_check_work_size(n, rows))
+
+
+def pbft_check(suite, data, data_off, pre_flags, msg_weight, checks, msg_row, prop_row, prep_off, prep_row_off,
+               row_hash, sig, row_weight, quorum, msg_hash, msg_flags, prepared_check, work, given=None,
+               given_mask=None, row_slot=None, row_pub=None, groups=None, sig_ok=None, stream=None):
+    """The signature checks of n PBFT messages over `rows` signature rows (bcosgpu_pbft_check_dev): data uint8[B],
+    data_off int64[n+1], pre_flags uint8[n], msg_weight int64[n] (read as u64), checks uint8[n], msg_row /
+    prop_row int64[n], prep_off int64[n+1], prep_row_off int64[nprep+1], row_hash uint8[rows,32] (in / out: the
+    message rows are written), sig uint8[rows,64], row_weight int64[rows] (read as u64), exactly one of row_slot
+    int32[rows] / row_pub uint8[rows,64]; given uint8[n,32] with given_mask uint8[n], groups int64[ngroups,3]
+    and sig_ok uint8[rows] may be None -> msg_hash uint8[n,32], msg_flags int32[n], prepared_check uint8[nprep]."""
+    _dev(msg_hash)
+    n = data_off.numel() - 1
+    rows = row_weight.numel()
+    nprep = prep_row_off.numel() - 1
+    ngroups = groups.numel() // 3 if groups is not None else 0
+    check(lib().bcosgpu_pbft_check_dev(suite, _p(data), _p(data_off), _p(given), _p(given_mask), _p(pre_flags),
+                                       _p(msg_weight), _p(checks), _p(msg_row), _p(prop_row), _p(prep_off),
+                                       _p(prep_row_off), nprep, _p(row_hash), _p(sig), _p(row_weight), _p(row_slot),
+                                       _p(row_pub), _p(groups) if ngroups else None, ngroups, quorum, n, rows,
+                                       _p(msg_hash), _p(msg_flags), _p(prepared_check), _p(sig_ok), _p(work),
+                                       work.numel() * work.element_size(), _s(stream)))
+
+
 def merkle_size(n, width):
     return int(lib().bcosgpu_merkle_size(n, width))
 

@@ -518,6 +518,125 @@ int bcosgpu_headers_check(int suite, const bcosgpu_BlockHeaderData* headers, siz
                           int64_t prev_number, int flags, uint8_t* hash32, uint8_t* check, uint8_t* link,
                           uint8_t* sig_ok_or_null);
 
+/* ---------------------------------------------------------------- PBFT messages (a drained queue in one call) */
+/* Every signature of every message a PBFT worker popped from its queue, in one call, with the verdicts the
+ * handlers then read instead of verifying one signature at a time (PBFTEngine::executeWorker,
+ * bcos-pbft/bcos-pbft/pbft/engine/PBFTEngine.cpp:555-601):
+ *   the message signature     checkSignature, PBFTEngine.cpp:732-750
+ *   the proposal signature    checkProposalSignature, :752-771 (also called at :971 and :1417)
+ *   a prepared proposal       PBFTCacheProcessor::checkPrecommitWeight, pbft/cache/PBFTCacheProcessor.cpp:795-821
+ *                             (from isValidViewChangeMsg, PBFTEngine.cpp:1161-1178)
+ *   a NewView                 isValidNewViewMsg, PBFTEngine.cpp:1238-1263: every view change valid, and their
+ *                             nodes' weight against minRequiredQuorum()
+ * What stays on the host is everything stateful: the views and the committed index (PBFTEngine.cpp:1120-1160,
+ * :1232, PBFTCacheProcessor.cpp:763-770) and the second look at the cached precommit (:776-792).  That look
+ * never rescues a failed proposal -- checkPrecommitMsg returns the first result either way -- it only decides
+ * whether the local cache entry is erased; a handler that finds prepared_check != 0 for a proposal it has
+ * cached still runs it, as before.
+ * Views, nothing copied until packing: */
+typedef struct {                      /* a prepared (precommitted) proposal and its proof, PBFT.proto PBFTRawProposal */
+    const uint8_t* hash; size_t hash_len;                    /* PBFTProposal::hash(); <= 32 bytes, zero-filled */
+    const bcosgpu_HeaderSignature* proofs; size_t nproofs;   /* nodeList[i], signatureList[i] */
+} bcosgpu_PrecommitProof;
+#define BCOSGPU_PBFT_CHECK_MSG_SIG 1u
+#define BCOSGPU_PBFT_CHECK_PROPOSAL_SIG 2u
+#define BCOSGPU_PBFT_CHECK_PREPARED 4u
+typedef struct {
+    int64_t generated_from;
+    /* what the signature is over: hashFieldsData (PBFTMessage.cpp:92-98) or the codec payLoad
+     * (PBFTCodec.cpp:94-103).  Hashed on the device by ONE lane: meant for hashFieldsData, tens of bytes.  The
+     * sender of a payload-signed packet (ViewChange, NewView: up to hundreds of kilobytes) passes the hash the
+     * codec already computed as signature_hash instead. */
+    const uint8_t* signed_data; size_t signed_data_len;
+    /* non-empty: it IS signatureDataHash and signed_data is not hashed (a view change inside a NewView carries
+     * it, BaseMessage field 7); <= 32 bytes, zero-filled, as a header's dataHash */
+    const uint8_t* signature_hash; size_t signature_hash_len;
+    const uint8_t* signature; size_t signature_len;
+    const uint8_t* proposal_hash; size_t proposal_hash_len;   /* consensusProposal()->hash(); <= 32 bytes */
+    const uint8_t* proposal_signature; size_t proposal_signature_len;
+    const bcosgpu_PrecommitProof* prepared; size_t nprepared;
+    uint32_t checks;                  /* BCOSGPU_PBFT_CHECK_MSG_SIG | _PROPOSAL_SIG | _PREPARED */
+} bcosgpu_PBFTMessageData;
+typedef struct { size_t parent, first, count; } bcosgpu_PBFTGroup;  /* a NewView at `parent`, its view changes at [first, first+count) */
+/* msg_flags[i] is a bit set; message i is accepted iff it is 0.  The reference only ever returns false, so the
+ * bits have no precedence:
+ *    1  generated_from names no consensus node, negative included (getConsensusNodeByIndex,
+ *       ConsensusConfig.cpp:150-158).  Set whatever `checks` asks for; a requested signature of such a message
+ *       has no key and fails too (2, 4).
+ *    2  the message signature fails (PBFTEngine.cpp:743-748)
+ *    4  the proposal signature is absent (length 0) or fails (:755-758, :769-770)
+ *    8  a prepared proposal fails (:1171-1177): its prepared_check is 1 or 2
+ *   16  a view change of the group fails, i.e. its own bits 1-8 are not all 0 (:1243-1248)
+ *   32  the group's weight is below min_required_quorum (:1249-1262): the sum, per view change, of the weight
+ *       of its generated_from node; a view change whose node is unknown adds nothing
+ * prepared_check[] has one entry per prepared proposal, messages back to back:
+ *    0 passed   1 a proof names no node or fails (PBFTCacheProcessor.cpp:805-816)   2 weight below the quorum
+ *    (:820)     3 not checked (the message's checks lack BCOSGPU_PBFT_CHECK_PREPARED)
+ * The rows follow the header check's rules, for the same reason: ONE failed proof fails the proposal whatever
+ * the remaining weight (1 before 2); a node index listed twice counts twice; a signature shorter than 64
+ * bytes fails its row without a key; every row is verified, also those after a failed one. */
+#define BCOSGPU_PBFT_E_NODE 1u
+#define BCOSGPU_PBFT_E_MSG_SIG 2u
+#define BCOSGPU_PBFT_E_PROPOSAL_SIG 4u
+#define BCOSGPU_PBFT_E_PREPARED 8u
+#define BCOSGPU_PBFT_E_VIEWCHANGE 16u
+#define BCOSGPU_PBFT_E_GROUP_QUORUM 32u
+#define BCOSGPU_PREPARED_OK 0
+#define BCOSGPU_PREPARED_E_PROOF 1
+#define BCOSGPU_PREPARED_E_QUORUM 2
+#define BCOSGPU_PREPARED_UNCHECKED 3
+/* Bytes of d_work (4-byte aligned) for bcosgpu_pbft_check_dev over n messages with `rows` signature rows. */
+uint64_t bcosgpu_pbft_check_work_size(size_t n, size_t rows);
+/* The device path, stream-ordered, four phases on the one stream: pbft_hash_kernel (one message per lane: the
+ * digest of d_data[d_data_off[i] .. d_data_off[i+1]), or d_given32 + 32 i where d_given_mask[i] is set, to
+ * d_msg_hash32 and to the message's signature row of d_row_hash32), the existing known-key verify kernels over
+ * all rows (the registered-key kernel when d_row_slot is given, the generic one when d_row_pub64 is: exactly
+ * one of the two), pbft_verdict_kernel (one message per lane: its rows, its prepared proposals -- all proofs
+ * ok, and the wrapping u64 sum of their weights against `quorum` -- into bits 1-8 and d_prepared_check) and,
+ * when ngroups > 0, pbft_group_kernel (one group per lane: bits 16 and 32 into the parent).  The hasher
+ * follows the suite.  All pointers are device pointers; hash arrays, d_msg_flags and d_work are 4-byte aligned,
+ * 64-bit arrays 8-byte aligned:
+ *   d_given32 [32 n], d_given_mask [n]   both nullable: the given signatureDataHash of a message
+ *   d_pre_flags [n]                      the host's bits: BCOSGPU_PBFT_E_NODE where generated_from names no node
+ *   d_msg_weight [n] (u64)               the weight of the generated_from node, 0 where unknown (the group sum)
+ *   d_checks [n]                         BCOSGPU_PBFT_CHECK_* of each message
+ *   d_msg_row, d_prop_row [n] (i64)      the row of the message / proposal signature; a requested check whose
+ *                                        row is not in [0, rows) fails (an absent proposal signature: -1)
+ *   d_prep_off [n + 1]                   CSR: message i's prepared proposals are [d_prep_off[i], d_prep_off[i+1])
+ *   d_prep_row_off [nprep + 1]           CSR: prepared proposal p's proof rows are [d_prep_row_off[p],
+ *                                        d_prep_row_off[p+1]), so the proof rows lie back to back in the order of
+ *                                        the prepared proposals; nprep = d_prep_off[n]; a message without
+ *                                        BCOSGPU_PBFT_CHECK_PREPARED gets 3 and its rows are not read
+ *   d_row_hash32 [32 rows]               IN/OUT: the hashes of the proposal and proof rows, given; the message
+ *                                        rows are written by the call
+ *   d_sig [64 rows]                      r || s of each row;  d_row_weight [rows] (u64)
+ *   d_row_slot [rows] (ids of bcosgpu_register_keys; a negative or stale id fails its row) or d_row_pub64 [64 rows]
+ *   d_groups [3 ngroups] (u64)           parent, first, count of each group; nullable when ngroups == 0.  A
+ *                                        parent >= n is skipped, a range is clipped to n
+ * Outputs d_msg_hash32 [32 n], d_msg_flags [n] (u32), d_prepared_check [nprep], d_sig_ok [rows] (nullable).
+ * d_work's earlier contents do not matter.  n, rows, nprep and every data length must be below 2^32. */
+int bcosgpu_pbft_check_dev(int suite, const uint8_t* d_data, const uint64_t* d_data_off, const uint8_t* d_given32,
+                           const uint8_t* d_given_mask, const uint8_t* d_pre_flags, const uint64_t* d_msg_weight,
+                           const uint8_t* d_checks, const int64_t* d_msg_row, const int64_t* d_prop_row,
+                           const uint64_t* d_prep_off, const uint64_t* d_prep_row_off, size_t nprep,
+                           uint8_t* d_row_hash32, const uint8_t* d_sig, const uint64_t* d_row_weight,
+                           const int32_t* d_row_slot, const uint8_t* d_row_pub64, const uint64_t* d_groups,
+                           size_t ngroups, uint64_t quorum, size_t n, size_t rows, uint8_t* d_msg_hash32,
+                           uint32_t* d_msg_flags, uint8_t* d_prepared_check, uint8_t* d_sig_ok, void* d_work,
+                           uint64_t work_bytes, void* stream);
+/* The same from host views, on the calling thread's device: generated_from and every proof index mapped to the
+ * consensus key and weight, the consensus keys registered (a cached key is a lookup; when the cache cannot hold
+ * them all the rows carry the keys instead), everything packed into pinned staging, one H2D copy, the phases,
+ * one D2H copy.  Each requested signature is one row.  consensus->committed_index is not read.  `flags` is
+ * reserved (0).  msg_hash32 [32 n], msg_flags [n]; prepared_check (nullable) one entry per prepared proposal;
+ * sig_ok (nullable) has, per message, 2 + (its proofs) entries -- the message signature, the proposal
+ * signature, the proofs of every prepared proposal in order: 1 verified, 0 failed, 2 not requested.
+ * BCOSGPU_E_ARG for a null field with a length, a hash longer than 32 bytes, signed_data of 2^32 - 1 bytes or
+ * more, or a group that names messages outside [0, n).  n == 0 is a no-op. */
+int bcosgpu_pbft_check(int suite, const bcosgpu_PBFTMessageData* msgs, size_t n, const bcosgpu_PBFTGroup* groups,
+                       size_t ngroups, const bcosgpu_ConsensusSet* consensus, int flags, uint8_t* msg_hash32,
+                       uint32_t* msg_flags, uint8_t* prepared_check_or_null, uint8_t* sig_ok_or_null);
+
 /* ---------------------------------------------------------------- single calls on an explicit device */
 /* One signature per call, for the reference's per-transaction call sites: TxPool's submitter threads
  * (TxPool.h:48-49) -> TxValidator::verify (TxValidator.cpp:56) -> Transaction::verify (Transaction.h:68-82)

@@ -320,6 +320,44 @@ inline BlockHeaderCheck checkBlockHeaders(const std::vector<bcosgpu_BlockHeaderD
     return r;
 }
 
+/* What checkPBFTMessages returns: per message its signatureDataHash and its verdict bits (BCOSGPU_PBFT_E_*;
+ * accepted iff 0); per prepared proposal, messages back to back, BCOSGPU_PREPARED_*; per message 2 + (its
+ * proofs) signature verdicts (message signature, proposal signature, proofs): 1 verified / 0 failed / 2 not
+ * requested. */
+struct PBFTMessageCheck {
+    std::vector<HashType> hashes;
+    std::vector<uint32_t> flags;
+    std::vector<uint8_t> preparedCheck, sigOk;
+    bool accepted(size_t i) const { return flags[i] == 0; }
+};
+
+/* Every signature of the messages a PBFT worker drained from its queue, in one engine call: checkSignature and
+ * checkProposalSignature (PBFTEngine.cpp:732-771), checkPrecommitWeight (PBFTCacheProcessor.cpp:795-821) and the
+ * view-change loop of isValidNewViewMsg (PBFTEngine.cpp:1238-1263; groups: a NewView and its view changes).
+ * The handlers then read the verdicts; the views, the committed index and the second look at the cached precommit stay
+ * theirs.  SUITE: BCOSGPU_SUITE_*. */
+template <int SUITE>
+inline PBFTMessageCheck checkPBFTMessages(const std::vector<bcosgpu_PBFTMessageData>& msgs,
+                                          const bcosgpu_ConsensusSet& consensus,
+                                          const std::vector<bcosgpu_PBFTGroup>& groups = {}) {
+    const size_t n = msgs.size();
+    size_t nprep = 0, nsig = 0;
+    for (const bcosgpu_PBFTMessageData& m : msgs) {
+        nprep += m.nprepared;
+        nsig += 2;
+        for (size_t p = 0; p < m.nprepared; ++p) nsig += m.prepared[p].nproofs;
+    }
+    PBFTMessageCheck r;
+    r.hashes.assign(n, HashType{});
+    r.flags.assign(n, 0);
+    r.preparedCheck.assign(nprep, 0);
+    r.sigOk.assign(nsig, 0);
+    if (n == 0) return r;
+    check(bcosgpu_pbft_check(SUITE, msgs.data(), n, groups.data(), groups.size(), &consensus, 0, r.hashes[0].data(),
+                             r.flags.data(), nprep ? r.preparedCheck.data() : nullptr, r.sigOk.data()));
+    return r;
+}
+
 /* EVM ecRecover precompile(bcos-executor/src/vm/Precompiled.cpp:443-482): {true, 32-byte output}
  * on success, {true, {}} on failure; `in` is read as 128 zero-padded bytes. */
 inline std::pair<bool, bytes> ecRecover(const uint8_t* in, size_t len) {
