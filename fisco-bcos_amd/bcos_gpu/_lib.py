@@ -16,6 +16,8 @@ WEDPR_ENGINE_ERROR = -2
 KECCAK256, SM3 = 0, 1
 SUITE_SECP256K1, SUITE_SM2 = 0, 1
 MERKLE_NEW, MERKLE_OLD, MERKLE_NEW_BYTES = 0, 1, 2
+CIPHER_AES256, CIPHER_SM4 = 0, 1
+CBC_OK, CBC_E_LENGTH, CBC_E_PADDING = 0, 1, 2
 
 
 class BcosGpuError(RuntimeError):
@@ -83,6 +85,12 @@ _SIGS = {
     "bcosgpu_state_root_work_size": (ctypes.c_uint64, [_SZ]),
     "bcosgpu_state_root_dev": (_I, [_I, ctypes.c_uint32, _P, _P, _P, _SZ, _P, ctypes.c_uint64, _P, _P]),
     "bcosgpu_state_root": (_I, [_I, ctypes.c_uint32, _P, _SZ, _P]),
+    "bcosgpu_cbc_padded_size": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "bcosgpu_cbc_work_size": (ctypes.c_uint64, [_SZ]),
+    "bcosgpu_cbc_encrypt_batch_dev": (_I, [_I, _U8P, _SZ, _U8P, _SZ, _P, _P, _SZ, _P, _P, _P, ctypes.c_uint64, _P]),
+    "bcosgpu_cbc_decrypt_batch_dev": (_I, [_I, _U8P, _SZ, _U8P, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
+    "bcosgpu_cbc_encrypt_batch": (_I, [_I, _U8P, _SZ, _U8P, _SZ, _P, _SZ, _P, ctypes.c_uint64, _P]),
+    "bcosgpu_cbc_decrypt_batch": (_I, [_I, _U8P, _SZ, _U8P, _SZ, _P, _SZ, _P, ctypes.c_uint64, _P, _P]),
     "bcosgpu_header_preimage_size": (ctypes.c_uint64, [_P, _SZ, _I]),
     "bcosgpu_pack_header_preimages": (_I, [_P, _SZ, _I, _P, ctypes.c_uint64, _P]),
     "bcosgpu_headers_check_work_size": (ctypes.c_uint64, [_SZ, _SZ]),

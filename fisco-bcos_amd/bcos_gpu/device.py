@@ -50,6 +50,36 @@ def state_root(hasher, block_version, data, off3, kind, work, root, stream=None)
                                        work.numel() * work.element_size(), _p(root), _s(stream)))
 
 
+CIPHER_AES256, CIPHER_SM4 = _lib.CIPHER_AES256, _lib.CIPHER_SM4
+
+
+def cbc_work_size(n):
+    return int(lib().bcosgpu_cbc_work_size(n))
+
+
+def cbc_encrypt(cipher, key, data, offsets, out, out_off, work, iv=None, stream=None):
+    """CBC + PKCS#7 over n packed values under one key (bcosgpu_cbc_encrypt_batch_dev): key / iv host bytes
+    (iv None: the default IV), data uint8[B], offsets int64[n+1], out uint8[sum of (len // 16 + 1) * 16] (16-byte
+    aligned), out_off int64[n+1] (written), work uint8[>= cbc_work_size(n)]."""
+    _dev(out)
+    n = offsets.numel() - 1
+    assert out_off.numel() == n + 1
+    check(lib().bcosgpu_cbc_encrypt_batch_dev(cipher, key, len(key), iv, 0 if iv is None else len(iv), _p(data),
+                                              _p(offsets), n, _p(out), _p(out_off), _p(work),
+                                              work.numel() * work.element_size(), _s(stream)))
+
+
+def cbc_decrypt(cipher, key, data, offsets, out, out_len, status, iv=None, stream=None):
+    """The inverse over n packed ciphertexts (bcosgpu_cbc_decrypt_batch_dev): data uint8[B] (16-byte aligned),
+    offsets int64[n+1] (multiples of 16), out uint8[B] (not data: item i's plaintext at offsets[i], padding
+    included), out_len int32[n] (read as u32), status uint8[n] (0 ok, 1 bad length, 2 bad padding)."""
+    _dev(out)
+    n = offsets.numel() - 1
+    assert out_len.numel() == n and status.numel() == n
+    check(lib().bcosgpu_cbc_decrypt_batch_dev(cipher, key, len(key), iv, 0 if iv is None else len(iv), _p(data),
+                                              _p(offsets), n, _p(out), _p(out_len), _p(status), _s(stream)))
+
+
 def headers_check_work_size(n, rows):
     return int(lib().bcosgpu_headers_check_work_size(n, rows))
 

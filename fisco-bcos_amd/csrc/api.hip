@@ -428,6 +428,165 @@ int bcosgpu_state_root(int hasher, uint32_t block_version, const bcosgpu_StateEn
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ storage cipher (cipher_kernels.hip)
+namespace {
+
+// the checks every cipher entry point shares (0, or E_ARG with the message set); they need no device
+int check_cipher_key(int cipher_id, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len) {
+    if (cipher_id != BCOSGPU_CIPHER_AES256 && cipher_id != BCOSGPU_CIPHER_SM4) return set_err(BCOSGPU_E_ARG, "bad cipher");
+    if ((!key && key_len) || (!iv && iv_len)) return set_err(BCOSGPU_E_ARG, "null key or iv with a length");
+    return 0;
+}
+int check_value_views(const bcosgpu_Bytes* values, size_t n) {
+    if (n > 0xFFFFFFFFull) return set_err(BCOSGPU_E_ARG, "batch too large");
+    if (n && !values) return set_err(BCOSGPU_E_ARG, "null pointer");
+    for (size_t i = 0; i < n; ++i)
+        if ((!values[i].data && values[i].len) || values[i].len > 0xFFFFFFFFull)
+            return set_err(BCOSGPU_E_ARG, "bad value view (null data with a length, or a value of 4 GiB or more)");
+    return 0;
+}
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+uint64_t round16(uint64_t x) { return (x + 15) & ~15ull; }
+
+}  // namespace
+
+extern "C" {
+
+uint64_t bcosgpu_cbc_padded_size(uint64_t len) { return cipher::cbc_padded_size(len); }
+uint64_t bcosgpu_cbc_work_size(size_t n) { return cbc_work_bytes(n); }
+
+int bcosgpu_cbc_encrypt_batch_dev(int cipher_id, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                                  const uint8_t* d_in, const uint64_t* d_in_off, size_t n, uint8_t* d_out,
+                                  uint64_t* d_out_off, void* d_work, uint64_t work_bytes, void* stream) {
+    if (int rc = check_cipher_key(cipher_id, key, key_len, iv, iv_len)) return rc;
+    if (n == 0) return 0;
+    if (!d_in || !d_in_off || !d_out || !d_out_off || !d_work) return set_err(BCOSGPU_E_ARG, "null pointer");
+    if (!aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_work) & 7u))
+        return set_err(BCOSGPU_E_ARG, "d_out must be 16-byte aligned and d_work 8-byte aligned");
+    const cipher::Schedule ck = cipher::make_schedule(cipher_id, false, key, key_len, iv, iv_len);
+    const int rc = launch_cbc_encrypt(cipher_id, ck, d_in, d_in_off, n, d_out, d_out_off, d_work, work_bytes,
+                                      as_stream(stream));
+    if (rc == BCOSGPU_E_ARG) return set_err(rc, "work buffer too small or batch too large");
+    return rc ? hip_err(hipGetLastError(), "cbc encrypt launch") : 0;
+}
+
+int bcosgpu_cbc_decrypt_batch_dev(int cipher_id, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                                  const uint8_t* d_in, const uint64_t* d_in_off, size_t n, uint8_t* d_out,
+                                  uint32_t* d_out_len, uint8_t* d_status, void* stream) {
+    if (int rc = check_cipher_key(cipher_id, key, key_len, iv, iv_len)) return rc;
+    if (n == 0) return 0;
+    if (!d_in || !d_in_off || !d_out || !d_out_len || !d_status) return set_err(BCOSGPU_E_ARG, "null pointer");
+    if (d_in == d_out) return set_err(BCOSGPU_E_ARG, "input and output must not overlap");
+    if (!aligned16(d_in) || !aligned16(d_out)) return set_err(BCOSGPU_E_ARG, "d_in and d_out must be 16-byte aligned");
+    const cipher::Schedule ck = cipher::make_schedule(cipher_id, true, key, key_len, iv, iv_len);
+    const int rc = launch_cbc_decrypt(cipher_id, ck, d_in, d_in_off, n, d_out, d_out_len, d_status, as_stream(stream));
+    if (rc == BCOSGPU_E_ARG) return set_err(rc, "batch too large");
+    return rc ? hip_err(hipGetLastError(), "cbc decrypt launch") : 0;
+}
+
+// DataEncryption::encrypt over the values of a commit (RocksDBStorage.cpp:348-353, :513-524): the values are
+// gathered into pinned staging as off | data, one H2D, the kernels, the ciphertexts back in one copy.  The
+// output offsets are also computed here: the cap check needs them before anything runs.
+int bcosgpu_cbc_encrypt_batch(int cipher_id, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                              const bcosgpu_Bytes* values, size_t n, uint8_t* out, uint64_t cap, uint64_t* out_off) {
+    if (int rc = check_cipher_key(cipher_id, key, key_len, iv, iv_len)) return rc;
+    if (int rc = check_value_views(values, n)) return rc;
+    if (n == 0) return 0;
+    if (!out || !out_off) return set_err(BCOSGPU_E_ARG, "null pointer");
+    uint64_t bytes = 0, total = 0;
+    for (size_t i = 0; i < n; ++i) bytes += values[i].len, total += cipher::cbc_padded_size(values[i].len);
+    if (cap < total) return set_err(BCOSGPU_E_ARG, "cap too small");
+    const cipher::Schedule ck = cipher::make_schedule(cipher_id, false, key, key_len, iv, iv_len);
+    WsCall c;
+    if (c.rc) return c.rc;
+    Workspace* w = c.w;
+    const uint64_t offb = 8 * (static_cast<uint64_t>(n) + 1), in_bytes = offb + bytes, work = cbc_work_bytes(n);
+    HIP_OK(w->h[0].ensure(in_bytes + 16));
+    uint64_t* off = w->h[0].as<uint64_t>();
+    uint8_t* data = reinterpret_cast<uint8_t*>(off) + offb;
+    off[0] = out_off[0] = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (values[i].len) std::memcpy(data + off[i], values[i].data, values[i].len);
+        off[i + 1] = off[i] + values[i].len;
+        out_off[i + 1] = out_off[i] + cipher::cbc_padded_size(values[i].len);
+    }
+    HIP_OK(c.ensure({in_bytes + 16, total, offb, work}));
+    HIP_OK(c.h2d(0, off, in_bytes));
+    const int rc = launch_cbc_encrypt(cipher_id, ck, c.buf(0) + offb, c.buf<uint64_t>(0), n, c.buf(1), c.buf<uint64_t>(2),
+                                      c.buf<void>(3), work, c.stream());
+    if (rc) return hip_err(hipGetLastError(), "cbc encrypt launch");
+    HIP_OK(c.d2h(out, 1, total));
+    return c.finish();
+}
+
+// DataEncryption::decrypt over the values of a batched read (RocksDBStorage.cpp:106-108, :204-205): an item whose
+// length is not a non-zero multiple of 16 fails here, the rest are packed (their offsets stay multiples of 16)
+// and decrypted; the raw plaintext blocks, lengths and statuses come back in one copy and are compacted.
+int bcosgpu_cbc_decrypt_batch(int cipher_id, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                              const bcosgpu_Bytes* values, size_t n, uint8_t* out, uint64_t cap, uint64_t* out_off,
+                              uint8_t* status) {
+    if (int rc = check_cipher_key(cipher_id, key, key_len, iv, iv_len)) return rc;
+    if (int rc = check_value_views(values, n)) return rc;
+    if (n == 0) return 0;
+    if (!out_off || !status) return set_err(BCOSGPU_E_ARG, "null pointer");
+    uint64_t bytes = 0, m = 0;  // of the well-formed items
+    for (size_t i = 0; i < n; ++i)
+        if (values[i].len && values[i].len % 16 == 0) bytes += values[i].len, ++m;
+    if (cap < bytes || (bytes && !out)) return set_err(BCOSGPU_E_ARG, bytes && !out ? "null pointer" : "cap too small");
+    if (m == 0) {
+        for (size_t i = 0; i <= n; ++i) out_off[i] = 0;
+        std::memset(status, BCOSGPU_CBC_E_LENGTH, n);
+        return 0;
+    }
+    const cipher::Schedule ck = cipher::make_schedule(cipher_id, true, key, key_len, iv, iv_len);
+    WsCall c;
+    if (c.rc) return c.rc;
+    Workspace* w = c.w;
+    // staging in: data (16-byte aligned, first) | off[m+1]; back: plaintext blocks | out_len[m] | status[m]
+    const uint64_t offb = 8 * (m + 1), in_bytes = bytes + offb, back = bytes + 4 * m + m;
+    HIP_OK(w->h[0].ensure(in_bytes));
+    HIP_OK(w->h[1].ensure(back));
+    uint8_t* data = w->h[0].as<uint8_t>();
+    uint64_t* off = reinterpret_cast<uint64_t*>(data + bytes);
+    uint64_t at = 0, k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!values[i].len || values[i].len % 16) continue;
+        std::memcpy(data + at, values[i].data, values[i].len);
+        off[k++] = at;
+        at += values[i].len;
+    }
+    off[m] = at;
+    HIP_OK(c.ensure({in_bytes, back}));
+    HIP_OK(c.h2d(0, data, in_bytes));
+    uint8_t* d_back = c.buf(1);
+    const int rc = launch_cbc_decrypt(cipher_id, ck, c.buf(0), reinterpret_cast<const uint64_t*>(c.buf(0) + bytes), m,
+                                      d_back, reinterpret_cast<uint32_t*>(d_back + bytes), d_back + bytes + 4 * m,
+                                      c.stream());
+    if (rc) return hip_err(hipGetLastError(), "cbc decrypt launch");
+    HIP_OK(c.d2h(w->h[1].p, 1, back));
+    HIP_OK(hipStreamSynchronize(c.stream()));
+    const uint8_t* plain = w->h[1].as<uint8_t>();
+    const uint32_t* len = reinterpret_cast<const uint32_t*>(plain + bytes);
+    const uint8_t* st = plain + bytes + 4 * m;
+    out_off[0] = 0;
+    k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t got = 0;
+        if (!values[i].len || values[i].len % 16) {
+            status[i] = BCOSGPU_CBC_E_LENGTH;
+        } else {
+            status[i] = st[k];
+            got = st[k] == BCOSGPU_CBC_OK ? len[k] : 0;
+            if (got) std::memcpy(out + out_off[i], plain + off[k], got);
+            ++k;
+        }
+        out_off[i + 1] = out_off[i] + got;
+    }
+    return c.finish();
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------ signature rows against a consensus set
 namespace {
 

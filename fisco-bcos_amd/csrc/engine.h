@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../include/bcos_gpu.h"
 #include "host_rt.h"
+#include "cipher_host.h"
 
 namespace bcosgpu {
 
@@ -53,6 +54,15 @@ uint64_t state_root_work_bytes(uint64_t n);
 int launch_state_root(int hasher, uint32_t block_version, const uint8_t* d_data, const uint64_t* d_off3,
                       const uint8_t* d_kind, uint64_t n, void* d_work, uint64_t work_bytes, uint8_t* d_root,
                       hipStream_t st);
+
+// cipher_kernels.hip: CBC over packed storage values under one schedule (cipher_host.h's make_schedule: an
+// encrypt schedule for launch_cbc_encrypt, a decrypt schedule for launch_cbc_decrypt); all device pointers
+uint64_t cbc_work_bytes(uint64_t n);
+int launch_cbc_encrypt(int cipher_id, const cipher::Schedule& ck, const uint8_t* d_in, const uint64_t* d_in_off,
+                       uint64_t n, uint8_t* d_out, uint64_t* d_out_off, void* d_work, uint64_t work_bytes,
+                       hipStream_t st);
+int launch_cbc_decrypt(int cipher_id, const cipher::Schedule& ck, const uint8_t* d_in, const uint64_t* d_in_off,
+                       uint64_t n, uint8_t* d_out, uint32_t* d_out_len, uint8_t* d_status, hipStream_t st);
 
 // ecc_tables.hip, ecc_sig.hip, ecc_txv.hip (the ECC kernels: tables, signing, verify / recover launchers)
 int ecc_init_tables(int device, int small_tables);

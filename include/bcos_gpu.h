@@ -399,6 +399,74 @@ int bcosgpu_state_root_dev(int hasher, uint32_t block_version, const uint8_t* d_
 int bcosgpu_state_root(int hasher, uint32_t block_version, const bcosgpu_StateEntry* entries, size_t n,
                        uint8_t* root32);
 
+/* ---------------------------------------------------------------- storage cipher (DataEncryption over storage values) */
+/* The third member of the reference's CryptoSuite, SymmetricEncryption (bcos-crypto/bcos-crypto/interfaces/crypto/
+ * CryptoSuite.h:33-67), at its batch sites: with storage_security.enable=true RocksDBStorage runs every non-empty
+ * value through DataEncryption::encrypt on the way to disk (asyncPrepare, bcos-storage/bcos-storage/
+ * RocksDBStorage.cpp:348-353; setRows, :513-524) and through decrypt on the way back (asyncGetRow, :106-108;
+ * asyncGetRows, :204-205).  DataEncryption (bcos-security/bcos-security/DataEncryption.cpp:143-165) calls
+ * symmetricEncrypt / symmetricDecrypt(data, size, key, keySize), i.e. AESCrypto / SM4Crypto
+ * (bcos-crypto/bcos-crypto/encrypt/AESCrypto.cpp:29-51, SM4Crypto.cpp:28-49) over wedpr's AES-256-CBC / SM4-CBC.
+ *   key     the first min(key_len, K) bytes, zero-filled to K; K = 32 (AES-256), 16 (SM4)
+ *           (bcos-utilities/bcos-utilities/FixedBytes.h:173-176, AESCrypto.cpp:34, SM4Crypto.cpp:33); a longer key is
+ *           cut (bcos-crypto/test/unittests/EncryptionTest.cpp:73 passes 69 bytes)
+ *   iv      iv != NULL: its first min(iv_len, 16) bytes, zero-filled to 16 (AESCrypto.cpp:37, SM4Crypto.cpp:36).
+ *           iv == NULL: the default IV of the two-argument form DataEncryption uses (AESCrypto.h:41-51,
+ *           SM4Crypto.h:41-50), the first 16 bytes of the raw key.  STATED DEVIATION: with a key shorter than 16
+ *           bytes the reference reads past the end of the caller's buffer (the key "abcd" of EncryptionTest.cpp:38
+ *           does); this build zero-fills instead.
+ *   mode    CBC with PKCS#7 padding: len bytes become (len / 16 + 1) * 16, an empty value one block (the reference
+ *           sizes its buffer len + 26 and shrinks it to what wedpr reports, AESCrypto.cpp:41-49).  The RocksDB sites
+ *           skip empty values themselves (!value.empty()): that is the adapter's job (bcos_gpu.hpp), not this call's.
+ *   decrypt fails per item, as a status byte, where the reference throws DecryptException (AESCrypto.cpp:69-72): a
+ *           length that is zero or no multiple of 16, a last plaintext byte p outside 1..16, or last p bytes that are
+ *           not all p.  It never fails the call.
+ * Parity unpinned: mode and padding live in wedpr (Rust), which is not built here, and the reference's
+ * only test is a round trip (EncryptionTest.cpp:35-92).  The ciphers are pinned by FIPS-197 C.3, SP 800-38A
+ * F.2.5 / F.2.6 and GB/T 32907 A.1, CBC and the padding by OpenSSL's output (tests/golden/cipher.json). */
+#define BCOSGPU_CIPHER_AES256 0
+#define BCOSGPU_CIPHER_SM4 1
+#define BCOSGPU_CBC_OK 0
+#define BCOSGPU_CBC_E_LENGTH 1
+#define BCOSGPU_CBC_E_PADDING 2
+/* The ciphertext bytes of a value of len bytes: (len / 16 + 1) * 16. */
+uint64_t bcosgpu_cbc_padded_size(uint64_t len);
+/* Bytes of d_work (8-byte aligned) for bcosgpu_cbc_encrypt_batch_dev over n values. */
+uint64_t bcosgpu_cbc_work_size(size_t n);
+/* Encrypts n packed values (d_in, value i at d_in_off[i] .. d_in_off[i+1], any byte offsets) under one key,
+ * stream-ordered.  key and iv are HOST pointers (iv == NULL: the default IV); the schedule is expanded on the host
+ * and travels in the kernel arguments.  Writes d_out_off[n+1] (d_out_off[i] = 16 * the blocks of the values before
+ * i, d_out_off[n] the total) and the ciphertexts at those offsets of d_out, which must be 16-byte aligned and hold
+ * the sum of bcosgpu_cbc_padded_size over the values.  One lane runs one value; a value of more than 1 KiB is
+ * listed in d_work and run by a second launch, so that long values share waves.  d_work's earlier contents do not
+ * matter.  n and every value's length must be below 2^32.  n == 0 writes nothing. */
+int bcosgpu_cbc_encrypt_batch_dev(int cipher, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                                  const uint8_t* d_in, const uint64_t* d_in_off, size_t n, uint8_t* d_out,
+                                  uint64_t* d_out_off, void* d_work, uint64_t work_bytes, void* stream);
+/* Decrypts n packed ciphertexts (d_in 16-byte aligned, every d_in_off a multiple of 16: the layout the call above
+ * writes), stream-ordered, one lane per 16-byte block.  The plaintext of item i lands at d_out + d_in_off[i], padding
+ * included; d_out_len[i] (uint32) is its length without the padding and d_status[i] (uint8) BCOSGPU_CBC_OK, or
+ * d_out_len[i] = 0 with BCOSGPU_CBC_E_LENGTH (an empty item) or BCOSGPU_CBC_E_PADDING.  d_out must be 16-byte
+ * aligned, as large as d_in and must not overlap it (a lane reads its neighbour's ciphertext block):
+ * BCOSGPU_E_ARG when d_in == d_out. */
+int bcosgpu_cbc_decrypt_batch_dev(int cipher, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                                  const uint8_t* d_in, const uint64_t* d_in_off, size_t n, uint8_t* d_out,
+                                  uint32_t* d_out_len, uint8_t* d_status, void* stream);
+/* The same from host views: the values are gathered into pinned staging, one H2D copy, the kernels, one copy back.
+ * Encrypt: out (cap bytes) receives the ciphertexts back to back, out_off[n+1] their offsets (multiples of 16);
+ * BCOSGPU_E_ARG if cap is below the sum of bcosgpu_cbc_padded_size over the values.
+ * Decrypt: an item whose length is not a non-zero multiple of 16 gets BCOSGPU_CBC_E_LENGTH without reaching the
+ * GPU; out receives the plaintexts back to back (nothing for a failed item), out_off[n+1] their offsets, status[n]
+ * the BCOSGPU_CBC_* of each item; BCOSGPU_E_ARG if cap is below the sum of the well-formed items' lengths (always
+ * enough: a plaintext is shorter than its ciphertext).
+ * Both: BCOSGPU_E_ARG for an unknown cipher, a null pointer with a non-zero length, or n or a value of 2^32 or
+ * more; n == 0 succeeds and writes nothing. */
+int bcosgpu_cbc_encrypt_batch(int cipher, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                              const bcosgpu_Bytes* values, size_t n, uint8_t* out, uint64_t cap, uint64_t* out_off);
+int bcosgpu_cbc_decrypt_batch(int cipher, const uint8_t* key, size_t key_len, const uint8_t* iv, size_t iv_len,
+                              const bcosgpu_Bytes* values, size_t n, uint8_t* out, uint64_t cap, uint64_t* out_off,
+                              uint8_t* status);
+
 /* ---------------------------------------------------------------- block headers (hash, parent link, quorum) */
 /* The check a syncing node runs on every downloaded block, for a run of consecutive headers in one call:
  *   the header hash    impl_calculate<Hasher>(bcostars::BlockHeader), bcos-tars-protocol/.../impl/TarsHashable.h:77-126

@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <utility>
 #include <vector>
 
@@ -264,6 +265,70 @@ inline HashType calculateStateRoot(const std::vector<bcosgpu_StateEntry>& entrie
     HashType root{};
     check(bcosgpu_state_root(HASHER, blockVersion, entries.data(), entries.size(), root.data()));
     return root;
+}
+
+/* DataEncryption::encrypt over the values of a storage write (bcos-security/bcos-security/DataEncryption.cpp:143-165:
+ * AES-256-CBC or SM4-CBC under the data key, the default IV), for the batch sites of RocksDBStorage with
+ * storage_security.enable=true:
+ *   asyncPrepare   bcos-storage/bcos-storage/RocksDBStorage.cpp:348-353   the block commit's dirty entries
+ *   setRows        :513-524
+ * out[i] is the ciphertext of values[i].  With skipEmpty an empty value stays empty, as asyncPrepare's
+ * `!value.empty()` leaves it (:348); setRows has no such test (:518-522) and passes skipEmpty = false, which
+ * turns an empty value into one padding block.  CIPHER: BCOSGPU_CIPHER_AES256 / BCOSGPU_CIPHER_SM4. */
+template <int CIPHER>
+inline std::vector<std::string> encryptStorageValues(std::string_view dataKey, const std::vector<std::string_view>& values,
+                                                     bool skipEmpty = true) {
+    std::vector<bcosgpu_Bytes> views;
+    std::vector<size_t> index;
+    uint64_t cap = 0;
+    for (size_t i = 0; i < values.size(); ++i) {
+        if (skipEmpty && values[i].empty()) continue;
+        views.push_back({reinterpret_cast<const uint8_t*>(values[i].data()), values[i].size()});
+        index.push_back(i);
+        cap += bcosgpu_cbc_padded_size(values[i].size());
+    }
+    std::vector<std::string> out(values.size());
+    if (views.empty()) return out;
+    bytes packed(cap);
+    std::vector<uint64_t> off(views.size() + 1);
+    check(bcosgpu_cbc_encrypt_batch(CIPHER, reinterpret_cast<const uint8_t*>(dataKey.data()), dataKey.size(), nullptr, 0,
+                                    views.data(), views.size(), packed.data(), cap, off.data()));
+    for (size_t k = 0; k < index.size(); ++k)
+        out[index[k]].assign(reinterpret_cast<const char*>(packed.data() + off[k]), off[k + 1] - off[k]);
+    return out;
+}
+
+/* DataEncryption::decrypt over the values of a read -- asyncGetRow (RocksDBStorage.cpp:106-108) and the batched
+ * asyncGetRows (:204-205).  An empty value stays empty, as both sites leave it.  status[i] is BCOSGPU_CBC_OK, or
+ * BCOSGPU_CBC_E_LENGTH / BCOSGPU_CBC_E_PADDING with an empty values[i] where the reference throws
+ * DecryptException (bcos-crypto/bcos-crypto/encrypt/AESCrypto.cpp:69-72): the caller throws for the rows it needs. */
+struct DecryptedStorageValues {
+    std::vector<std::string> values;
+    std::vector<uint8_t> status;
+};
+template <int CIPHER>
+inline DecryptedStorageValues decryptStorageValues(std::string_view dataKey, const std::vector<std::string_view>& values) {
+    std::vector<bcosgpu_Bytes> views;
+    std::vector<size_t> index;
+    uint64_t cap = 0;
+    for (size_t i = 0; i < values.size(); ++i) {
+        if (values[i].empty()) continue;
+        views.push_back({reinterpret_cast<const uint8_t*>(values[i].data()), values[i].size()});
+        index.push_back(i);
+        cap += values[i].size();
+    }
+    DecryptedStorageValues r{std::vector<std::string>(values.size()), std::vector<uint8_t>(values.size(), BCOSGPU_CBC_OK)};
+    if (views.empty()) return r;
+    bytes packed(cap);
+    std::vector<uint64_t> off(views.size() + 1);
+    std::vector<uint8_t> st(views.size());
+    check(bcosgpu_cbc_decrypt_batch(CIPHER, reinterpret_cast<const uint8_t*>(dataKey.data()), dataKey.size(), nullptr, 0,
+                                    views.data(), views.size(), packed.data(), cap, off.data(), st.data()));
+    for (size_t k = 0; k < index.size(); ++k) {
+        r.values[index[k]].assign(reinterpret_cast<const char*>(packed.data() + off[k]), off[k + 1] - off[k]);
+        r.status[index[k]] = st[k];
+    }
+    return r;
 }
 
 /* BlockHeader::hash -- impl_calculate<Hasher>(bcostars::BlockHeader) (TarsHashable.h:77-126) for a run of
