@@ -240,7 +240,8 @@ __global__ __launch_bounds__(256, 1) void tx_verify_split_kernel(const uint8_t* 
 // the square root and the comb windows of u1*G run side by side on the four waves, and phase C is
 // the two cooperative GLV chains only.  Bit-identical to tx_verify_kernel<0, *>.
 #ifdef BCOSGPU_COOP_TIMING  // tools/coopbench.hip: phase timestamps of workgroup 0
-__device__ uint64_t g_coop_t[4][8];
+// [wave][stamp]: eight waves and stamps 8 .. 10 are the lane-trio recovery kernel's (trio26_recover_body)
+__device__ uint64_t g_coop_t[8][12];
 __device__ uint64_t g_dbl_t[4][8];
 #define DBL_T(k) \
     if (c.probe && (threadIdx.x & 63) == 0) g_dbl_t[threadIdx.x >> 6][k] = clock64()
@@ -1014,17 +1015,31 @@ struct Trio26Lds {
     uint32_t post[3];
 };
 struct Trio26RecoverLds : Trio26Lds {
-    // the split square root: the head's live elements (0..4) and w (5), raw limbs, from phase A's wave 2
-    // to phase D's chain-1 waves; and their verdict y^2 = w
-    uint32_t sq[6][10][40];
+    // the square root, raw limbs: w = x^3 + 7 (0) and y (1, normalized, v's parity), from the root's helper
+    // to phase D; and its verdict y^2 = w
+    uint32_t sq[2][10][40];
     uint32_t yok[64];
-    // no barrier separates the phases up to phase D's last addition (the chain-1 waves, which leave
-    // phase A first, run ahead and sum the comb partials early), so the hand-offs are flags:
-    // 0 table, k and flags ready (wave 1); 1 + w: wave w's comb partial stored; 5 + p: wave pair p's chain-1
-    // point stored.  The points then cannot reuse the table's LDS: xg holds them ([pair] chain point /
-    // sum S / X3 Y3, [2 + pair] the G part).
+    // The kernel runs eight waves: 0..3 the chains (wave w: chain w & 1 of txs 20 (w >> 1) .. + 19), 4..7
+    // the helpers (one lane per tx; helper h = wave - 4 shares a SIMD with wave h).  No barrier separates
+    // the phases up to phase D's first one, so the hand-offs are one-way flags (lds_flag_post: a release
+    // store of 1; the waiter's acquire loads with s_sleep between them):
+    //   flag       posted by                waited for by                guards
+    //   post[0]    wave 0                   helpers with comb windows    xrinv (r^-1 mod n)
+    //   post[1]    helper 3                 helpers with comb windows    xe (the digest mod n)
+    //   spost[0]   wave 0                   waves 0..3, before phase C   k, flags (the GLV halves of s / r)
+    //   spost[1]   wave 1                   waves 0..3, before phase C   tab, tabphx, zc (the table of R')
+    //   spost[2]   helper 2                 waves 0, 2, in phase D       sq, rflag, yok (w, y, the verdicts)
+    //   spost[5+p] wave 2 p + 1             wave 2 p, in phase D         xg[p] (pair p's chain-1 point)
+    //   hpost[j]   the j-th summing helper  the j + 1-th                 pt[j] (the comb partials so far)
+    // The last summing helper leaves the G part in pt[3]; it and wave 1..3's other reads of helper results
+    // lie behind phase D's first barrier, which the helpers join after their last store.  The rule: no wave
+    // waits for a flag whose poster can be parked at a barrier that needs the waiter.  Every poster above
+    // posts before its first barrier after the start, and waits before that only for flags higher in this
+    // table (wave 0 and helper 3 for none; wave 1 for none).
+    // The chain points cannot reuse the table's LDS: xg holds them ([pair] chain point / sum S / X3 Y3).
     uint32_t spost[8];
-    uint32_t xg[4][kTrioWords][64];
+    uint32_t hpost[4];
+    uint32_t xg[2][kTrioWords][64];
 };
 __device__ __forceinline__ void lds_store_limbs26(uint32_t (*dst)[64], const fe26& a, int lane) {
     fe26 t;
@@ -1138,15 +1153,16 @@ __device__ __forceinline__ void trio_sum_partials(TrioPt& A, const Trio26Lds& L,
 // ------------------------------------------------------------------ the three fe26 kernels
 // One body per kernel, phases shared as the functions below and above:
 //   coop26_body          tx_verify_coop26_kernel   recovery, 64 txs per workgroup, wave-pair chains
-//   trio26_recover_body  tx_verify_trio26_kernel   recovery, 40 txs per workgroup, lane-trio chains, the
-//                                                  square root split between phase A and phase D
+//   trio26_recover_body  tx_verify_trio26_kernel   recovery, 40 txs per workgroup, lane-trio chains on
+//                                                  four waves, four helper waves beside them
 //   trio26_verify_body   sig_verify_trio26_kernel  libsecp256k1 ecdsa_verify with a KNOWN key P (KeyIO) on
 //                                                  lane trios: Q = (e/s) G + (r/s) P, accept iff x(Q) = r mod n
 // Recovery computes Q = u1 G + u2 R with R from r and v; known-key verify needs no square root (P is
 // given), s^-1 instead of r^-1, and the projective x-check instead of the affine inversion and the
-// address hash.  Shared: recover_w (both recoveries), coop26_table_to_lds and the scalar phase
-// (coop26_post_e_inv, coop26_u1_glv; all three), comb_share (all three), trio_glv_chain and
-// trio_sum_partials (both trio kernels); trio_recover_tail names the recovery kernel's last phase.
+// address hash.  Shared: recover_w (both recoveries), comb_share (all three), trio_glv_chain (both trio
+// kernels); coop26_table_to_lds, the scalar phase (coop26_post_e_inv, coop26_u1_glv) and trio_sum_partials are
+// coop26_body's and trio26_verify_body's (the eight-wave recovery body has trio_table_staged, its own scalar
+// phase on wave 0 and trio_recover_helper); trio_recover_tail names the recovery kernel's last phase.
 
 // Recovery, waves 1 and 2: X = r (+ n when v & 2) as fe26 and w = X^3 + 7 (m 2); returns ok and, for
 // v & 2, r < p - n.  No LDS.
@@ -1286,18 +1302,19 @@ __device__ __forceinline__ void comb_share_range(Jac26& G, const fe& u1, const u
 }
 // The pair kernel (always on the 8-bit comb; wave 2 takes the square root): 12 / 12 / 8 to waves 0 / 3 / 1.
 constexpr int kPairShare[4][2] = {{0, 12}, {24, 32}, {0, 0}, {12, 24}};
-// Recovery on trios: waves 0 / 3 / 2 / 1 take windows [0, a) / [a, b) / [b, c) / [c, 16) of kTrioSplitWin =
-// a, b, c, doubled on the 8-bit comb: 7 / 6 / 3 / 0 (wave 2 joins after the root's head, wave 1 after the
-// table and the GLV split).  A wave with no window adds no partial in phase D.
-constexpr int kTrioSplitWin[3] = {7, 13, 16};
-static_assert(0 < kTrioSplitWin[0] && kTrioSplitWin[0] < kTrioSplitWin[1] && kTrioSplitWin[1] <= kTrioSplitWin[2] &&
+// Recovery on trios: the helpers take the comb, helpers 0 / 1 / 3 / 2 the windows [0, a) / [a, b) / [b, c) /
+// [c, 16) of kTrioSplitWin = a, b, c, doubled on the 8-bit comb: 5 / 5 / 6 / 0 (helper 3 joins after the
+// digest, helper 2 after the square root, which outlasts the others' windows).  They sum their partials
+// in that order, each adding its own to the sum so far; a helper with no window adds nothing.
+constexpr int kTrioSplitWin[3] = {5, 10, 16};
+static_assert(0 < kTrioSplitWin[0] && kTrioSplitWin[0] < kTrioSplitWin[1] && kTrioSplitWin[1] < kTrioSplitWin[2] &&
                   kTrioSplitWin[2] <= 16,
-              "comb windows of waves 0, 3, 2, 1");
+              "comb windows of helpers 0, 1, 3, 2");
 constexpr CombShare trio_recover_share() {
     const int a = kTrioSplitWin[0], b = kTrioSplitWin[1], c = kTrioSplitWin[2];
-    return {{{0, a}, {c, 16}, {b, c}, {a, b}}, {{0, 2 * a}, {2 * c, 32}, {2 * b, 2 * c}, {2 * a, 2 * b}}};
+    return {{{0, a}, {a, b}, {c, 16}, {b, c}}, {{0, 2 * a}, {2 * a, 2 * b}, {2 * c, 32}, {2 * b, 2 * c}}};
 }
-constexpr CombShare kTrioRecoverShare = trio_recover_share();
+constexpr CombShare kTrioRecoverShare = trio_recover_share();  // [helper]
 // Known-key verify: 6 / 4 / 5 / 1 to waves 0 / 3 / 2 / 1 (wave 1 builds the table first; wave 3 also adds wave
 // 0's partial), 11 / 8 / 11 / 2 on the 8-bit comb.
 constexpr CombShare kTrioVerifyShare = {{{0, 6}, {15, 16}, {10, 15}, {6, 10}}, {{0, 11}, {30, 32}, {19, 30}, {11, 19}}};
@@ -1509,18 +1526,177 @@ __device__ __forceinline__ void trio_recover_tail(const IO& io, uint32_t* mbuf, 
     }
 }
 
-// tx_verify_trio26_kernel.  The recovery square root y = w^((p+1)/4) is cut in two after x176
-// (fe26_sqrt_head<0> / fe26_sqrt_tail<0>): wave 2 runs the head in phase A and then takes comb windows like
-// the other waves; the chain-1 waves run the tail (78 S + 4 M) in phase D, beside the Z^-1 of the chain-0
-// waves, whose input does not depend on y.  No barrier separates the phases up to phase D's
-// last addition: the hand-offs are the flags of Trio26RecoverLds::spost.
+// coop26_table_to_lds<true> within the register budget of two waves per SIMD: the same multiples
+// (multiples8_26), the same co-Z rescale (coz_table26) and the same stores, value for value, but the eight
+// Jacobian multiples wait in the table's own LDS rows of column `lane` (X, Y raw limbs in L.tab[j], Z in
+// L.tabphx[j]; magnitudes as CurveK1x returns them: 10, 10, 2) instead of 240 registers, and each entry
+// replaces its multiple once that is read back.  A lane touches its own column only.
+__device__ __forceinline__ void trio_table_staged(Trio26RecoverLds& L, const Aff26& P, int lane) {
+    const auto put = [&](int j, const Jac26& J) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) {
+            L.tab[j][q][lane] = J.X.v[q];
+            L.tab[j][10 + q][lane] = J.Y.v[q];
+            L.tabphx[j][q][lane] = J.Z.v[q];
+        }
+    };
+    const auto get_z = [&](fe26& Z, int j) {
+#pragma unroll
+        for (int q = 0; q < 10; ++q) Z.v[q] = L.tabphx[j][q][lane];
+        F26_SETM(Z, 2);
+    };
+    {
+        Jac26 A, B, N;  // T[j] = (j + 1) P
+        CurveK1x::from_aff(B, P);
+        CurveK1x::dbl(A, B);      // 2 P
+        put(1, A);
+        CurveK1x::madd(B, A, P);  // 3 P
+        put(2, B);
+        CurveK1x::dbl(N, A);      // 4 P
+        put(3, N);
+        CurveK1x::dbl(A, B);      // 6 P
+        put(5, A);
+        CurveK1x::madd(B, A, P);  // 7 P
+        put(6, B);
+        CurveK1x::madd(B, N, P);  // 5 P
+        put(4, B);
+        CurveK1x::dbl(A, N);      // 8 P
+        put(7, A);
+    }
+    // s_j = Zc / Z_j from prefix products and a running suffix, the entries from the top down (coz_table26)
+    fe26 pre[7], suf, Zc, beta, Zj;
+    fe26_one(pre[0]);
+    get_z(pre[1], 1);
+    Unroll<2, 7>::run([&](auto J) {
+        get_z(Zj, J);
+        fe26_mul(pre[J], pre[J - 1], Zj);
+    });
+    get_z(Zj, 7);
+    fe26_mul(Zc, pre[6], Zj);
+    fe26_const(beta, kGlvBeta);
+    Unroll<0, 8>::run([&](auto J) {
+        constexpr int j = 7 - decltype(J)::value;
+        fe26 sj, s2, s3, X, Y, bx;
+        if constexpr (j == 0) {
+            fe26_copy(X, P.x);
+            fe26_copy(Y, P.y);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 10; ++q) {
+                X.v[q] = L.tab[j][q][lane];
+                Y.v[q] = L.tab[j][10 + q][lane];
+            }
+            F26_SETM(X, 10);
+            F26_SETM(Y, 10);
+            get_z(Zj, j);
+        }
+        if constexpr (j == 7) fe26_copy(sj, pre[6]);
+        else if constexpr (j <= 1) fe26_copy(sj, suf);
+        else fe26_mul(sj, pre[j - 1], suf);
+        if constexpr (j == 7) fe26_copy(suf, Zj);
+        else if constexpr (j >= 1) fe26_mul(suf, suf, Zj);
+        fe26_sqr(s2, sj);
+        fe26_mul(s3, s2, sj);
+        fe26_mul(X, X, s2);
+        fe26_mul(Y, Y, s3);
+        fe26_mul(bx, X, beta);
+        lds_store_limbs26(L.tab[j], X, lane);
+        lds_store_limbs26(L.tab[j] + 10, Y, lane);
+        lds_store_limbs26(L.tabphx[j], bx, lane);
+    });
+    lds_store_fe26(L.zc, Zc, lane);
+}
+
+// a helper's wait of the recovery kernel: as lds_flag_wait, with a longer sleep between the loads (the
+// helper shares its SIMD with a chain wave, and nothing it waits for is urgent)
+__device__ __forceinline__ void lds_flag_wait_idle(uint32_t* f) {
+    while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) __builtin_amdgcn_s_sleep(8);
+}
+
+// What helper h = wave - 4 of tx_verify_trio26_kernel does, one lane per tx, before it joins phase D's
+// barriers: helper 2 the square root y = w^((p+1)/4) (fe26_sqrt_cand end to end, the verdict y^2 = w, v's
+// parity) into L.sq / L.rflag / L.yok, helper 3 the digest mod n into L.xe; then every helper with comb
+// windows (kTrioRecoverShare) takes u1 = -e / r with wave 0's r^-1 and its windows of u1 G, and the helpers
+// sum their partials in the order 0, 1, 3, 2, the last one into L.pt[3].  r, v and ok are read by helper 2
+// only.  (Trio26RecoverLds has the flags.)
+template <class IO>
+__device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const IO& io, uint64_t i, bool active, bool ok,
+                                                    const fe& r, uint32_t v, const uint32_t* __restrict__ tab, int tab_bits,
+                                                    int h, int lane) {
+    constexpr bool kRootAdds = kTrioSplitWin[2] < 16;
+    constexpr int kLast = kRootAdds ? 3 : 2;  // the place in the summing order that stores the G part
+    if (h == 2) {
+        fe26 X, w, y, ny, t;
+        const bool okr = recover_w(X, w, r, v, ok);
+        fe26_sqrt_cand(y, w);
+        fe26_sqr(t, y);
+        fe26_sub<3>(t, t, w);
+        const bool on = fe26_is_zero(t);  // y^2 = w: r is the x of a curve point
+        fe26_normalize(y);
+        fe26_neg<2>(ny, y);
+        fe26_normalize(ny);
+        fe26_cmov(y, ny, (y.v[0] & 1u) != (v & 1u));
+        if (lane < kTrioTxs) {
+#pragma unroll
+            for (int q = 0; q < 10; ++q) {
+                L.sq[0][q][lane] = w.v[q];
+                L.sq[1][q][lane] = y.v[q];
+            }
+        }
+        L.rflag[lane] = okr ? 2u : 0u;
+        L.yok[lane] = on ? 1u : 0u;
+        lds_flag_post(&L.spost[2]);
+        COOP_T(6);
+    } else if (h == 3) {
+        fe e;
+        fe_zero(e);
+        if (active) io.template digest<KECCAK256>(i, e);
+        reduce_once(e, ParamN1::M);
+        lds_store_fe(L.xe, e, lane);
+        lds_flag_post(&L.post[1]);
+        COOP_T(7);
+    }
+    int lo, hi;
+    comb_share(lo, hi, kTrioRecoverShare.wide, h);
+    if (lo != hi) {
+        lds_flag_wait_idle(&L.post[0]);
+        lds_flag_wait_idle(&L.post[1]);
+        fe e, rinv, u1;
+        lds_load_fe(e, L.xe, lane);
+        lds_load_fe(rinv, L.xrinv, lane);
+        FieldN1::mul(u1, e, rinv);
+        FieldN1::neg(u1, u1);
+        Jac26 G;
+        comb_share_range(G, u1, tab, tab_bits, kTrioRecoverShare, h);
+        const int j = h == 0 ? 0 : h == 1 ? 1 : h == 3 ? 2 : 3;  // the place in the summing order
+        if (j > 0) {
+            Jac26 P, S;
+            lds_flag_wait_idle(&L.hpost[j - 1]);
+            coop26_load_jac(P, L.pt[j - 1], lane);
+            CurveK1x::add(S, P, G);
+            coop26_store_jac(L.pt[j == kLast ? 3 : j], S, lane);
+        } else {
+            coop26_store_jac(L.pt[0], G, lane);
+        }
+        if (j != kLast) lds_flag_post(&L.hpost[j]);
+        COOP_T(10);
+    }
+}
+
+// tx_verify_trio26_kernel, eight waves.  Waves 0..3 do only what the chains need: wave 0 r^-1 mod n and at
+// once u2 = s / r and its GLV split, wave 1 the table of R' = (w x, w^2); each enters phase C behind the two
+// flags of those.  Waves 4..7 are helpers (trio_recover_helper): the digest, u1, the comb windows of u1 G and
+// their sum, and the whole square root, all of it needed in phase D only.  A helper shares a SIMD with a
+// chain wave and takes the issue slots that a lone wave leaves empty (a gfx950 SIMD is 32 lanes wide: a
+// wave64 VALU op occupies it for 2 cycles and a lone wave issues one per 4).  The helpers join
+// every barrier of phase D and of trio_recover_tail and do nothing between them.
 template <class IO>
 __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, const uint32_t* __restrict__ tab,
                                                     int tab_bits) {
-    constexpr int kLive = fe26_sqrt_live<0>();
-    constexpr bool kWave2Adds = kTrioSplitWin[1] < kTrioSplitWin[2], kWave1Adds = kTrioSplitWin[2] < 16;
     __shared__ Trio26RecoverLds L;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (readfirstlane: the roles below are scalar branches)
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const bool helper = wave >= 4;
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + lane;
     const bool active = lane < kTrioTxs && i < n;
     COOP_T(0);
@@ -1530,75 +1706,82 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         L.post[2] = 0u;
 #pragma unroll
         for (int q = 0; q < 8; ++q) L.spost[q] = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) L.hpost[q] = 0u;
     }
     __syncthreads();
-    // ---------------------------------------------------------------- phase A
-    fe r, s;
-    uint32_t v = 0;
-    bool ok = false;
-    if (active) ok = io.rsv(i, r, s, v);
-    else { fe_zero(r); fe_zero(s); }
-    if (wave == 1 || wave == 2) {
-        fe26 X, rhs;
-        const bool okr = recover_w(X, rhs, r, v, ok);
-        if (wave == 2) {  // the root's head only; the verdict so far, and v's parity for the tail
-            fe26 st[kLive];
-            fe26_sqrt_head<0>(st, rhs);
-            if (lane < kTrioTxs) {
-#pragma unroll
-                for (int j = 0; j < kLive; ++j) {
-#pragma unroll
-                    for (int q = 0; q < 10; ++q) L.sq[j][q][lane] = st[j].v[q];
-                }
-#pragma unroll
-                for (int q = 0; q < 10; ++q) L.sq[5][q][lane] = rhs.v[q];
-            }
-            L.rflag[lane] = (okr ? 2u : 0u) | ((v & 1u) << 4);
-            COOP_T(6);
+    const TrioLane T(lane);
+    TrioSeat seat(wave, lane, T);
+    if (helper) seat.chain = 2;  // neither chain: a helper only joins the barriers from phase D on
+    const int chain = seat.chain, tl = seat.tl;
+    uint32_t tflags = 0;
+    TrioPt acc;
+    {
+        // ------------------------------------------------------------ phase A
+        fe r, s;
+        uint32_t v = 0;
+        bool ok = false;
+        fe_zero(r);
+        fe_zero(s);
+        if (active && (wave <= 1 || wave == 4 + 2)) ok = io.rsv(i, r, s, v);
+        if (helper) {
+            trio_recover_helper(L, io, i, active, ok, r, v, tab, tab_bits, wave - 4, lane);
+            COOP_T(1);
         } else {
-            Aff26 R;
-            fe26_mul(R.x, rhs, X);  // w x
-            fe26_sqr(R.y, rhs);     // w^2
-            coop26_table_to_lds<true>(L, R, lane);
-            COOP_T(6);
+            if (wave == 0) {  // r^-1 (Montgomery form) for the helpers' u1, then the chains' scalars
+                if (!ok) {    // r = 1, s = 0 keep the arithmetic of the rejected lanes well defined
+                    fe_zero(r);
+                    r.v[0] = 1;
+                    fe_zero(s);
+                }
+                fe rm, rinv, u2, k1, k2;
+                FieldN1::from_plain(rm, r);
+                FieldInv<FieldN1>::inv_pipe(rinv, rm);
+                lds_store_fe(L.xrinv, rinv, lane);
+                lds_flag_post(&L.post[0]);
+                COOP_T(7);
+                FieldN1::mul(u2, s, rinv);
+                bool neg1, neg2;
+                glv_split(k1, neg1, k2, neg2, u2);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    L.k[0][q][lane] = k1.v[q];
+                    L.k[1][q][lane] = k2.v[q];
+                }
+                L.flags[lane] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
+                lds_flag_post(&L.spost[0]);
+                COOP_T(8);
+            } else if (wave == 1) {
+                fe26 X, rhs;
+                recover_w(X, rhs, r, v, ok);
+                Aff26 R;
+                fe26_mul(R.x, rhs, X);  // w x
+                fe26_sqr(R.y, rhs);     // w^2
+                trio_table_staged(L, R, lane);
+                lds_flag_post(&L.spost[1]);
+                COOP_T(6);
+            }
+            COOP_T(1);
+            lds_flag_wait(&L.spost[0]);
+            lds_flag_wait(&L.spost[1]);
+            COOP_T(9);
+            // (the chain waves are the older wave of their SIMD and win its arbitration by age; one s_setprio
+            // for them here measured 0.3383 against 0.3393 ms with run-to-run spreads of 0.0011 and 0.0025:
+            // no difference, profiles/trio_helpers_ab.json)
+            // -------------------------------------------------------- phase C: one GLV chain per trio
+            tflags = L.flags[tl];  // (the root's rflag is read in phase D, behind a barrier)
+            trio_glv_chain(acc, L, chain, tl, tflags, T);
+            COOP_T(2);
         }
     }
-    coop26_post_e_inv<false, true>(L, io, i, active, ok, r, s, wave, lane);
-    {
-        fe u1;
-        coop26_u1_glv<false>(u1, L, ok, r, s, wave, lane);
-        if (wave == 1) lds_flag_post(&L.spost[0]);  // phase C may start: the table, Zc, k and the flags
-        Jac26 G;
-        int lo, hi;
-        comb_share(lo, hi, kTrioRecoverShare.wide, wave);
-        if (lo == hi) CurveK1x::set_inf(G);
-        else comb_share_range(G, u1, tab, tab_bits, kTrioRecoverShare, wave);
-        // no partial is added here: each wave's goes to phase D behind its own flag
-        coop26_store_jac(L.pt[wave == 0 ? 3 : wave == 3 ? 4 : wave == 2 ? 0 : 2], G, lane);
-        lds_flag_post(&L.spost[1 + wave]);
-    }
-    COOP_T(1);
-    // each wave enters phase C once wave 1 has posted the table and the scalars; what the other waves leave
-    // in LDS is read in phase D only, behind their own flags or a barrier
-    lds_flag_wait(&L.spost[0]);
-    // ---------------------------------------------------------------- phase C: one GLV chain per trio
-    const TrioLane T(lane);
-    const TrioSeat seat(wave, lane, T);
-    const int chain = seat.chain, tl = seat.tl;
-    const uint32_t tflags = L.flags[tl];  // (wave 2's rflag is read in phase D, behind a barrier)
-    TrioPt acc;
-    trio_glv_chain(acc, L, chain, tl, tflags, T);
-    COOP_T(2);
     // ---------------------------------------------------------------- phase D on the trios
     // The chains' sum S lies on E_w; with l = Zc y and K = l^2 = Zc^2 w it is the point (X K, Y K l, Z K) of E
     // (trio_scale_xz, trio_scale_y), whose X and Z hold no y.  So the Z of the last addition T + S_E (T the G
-    // part) needs no y: chain 0 computes it alone (trio_add_z) and starts Z^-1, while chain 1 finishes the
-    // root, runs the complete addition and hands over X3, Y3.  Chain 1's waves leave phase A, and so phase
-    // C, before chain 0's: they sum the comb partials in that lead, behind flags instead of barriers.  All
-    // additions are trio_add (6 product levels instead of 16 products on one lane).  Then the affine map
-    // on lane 2 of each trio, and trio_recover_tail.
-    uint32_t* const xbuf = &L.xg[wave >> 1][0][0];
-    uint32_t* const gbuf = &L.xg[2 + (wave >> 1)][0][0];
+    // part, the helpers' sum) needs no y: chain 0 computes it alone (trio_add_z) and starts Z^-1, while chain
+    // 1 runs the complete addition and hands over X3, Y3.  All additions are trio_add (6 product levels
+    // instead of 16 products on one lane).  Then the affine map on lane 2 of each trio, and
+    // trio_recover_tail.
+    uint32_t* const xbuf = &L.xg[(wave >> 1) & 1][0][0];
     uint32_t* const mbuf = &L.tabphx[0][0][0];  // [40][16] pubkey messages, then [40][8] digests
     const uint64_t ti = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + tl;
     const bool tactive = ti < n;
@@ -1607,87 +1790,70 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
     const auto load_zc_w = [&](fe26& zc, fe26& w) {
         lds_load_fe26(zc, L.zc, tl);
 #pragma unroll
-        for (int q = 0; q < 10; ++q) w.v[q] = L.sq[5][q][tl];
+        for (int q = 0; q < 10; ++q) w.v[q] = L.sq[0][q][tl];
         F26_SETM(w, 2);
+    };
+    const auto load_g = [&](TrioPt& G) {  // the G part, from the helpers' one-lane sum
+        Jac26 J;
+        coop26_load_jac(J, L.pt[3], tl);
+        trio_from_jac(G, J, T);
     };
     TrioPt SE;
     fe26 zi2, zi3;  // chain 0: Z^-2, Z^-3
     fe26_zero(zi2);
     fe26_zero(zi3);
-    if (chain == 1) {  // its chain's point to the partner; T = the sum of phase A's comb partials
+    if (chain == 1) {  // its chain's point to the partner
         trio_store(xbuf, acc, lane);
         lds_flag_post(&L.spost[5 + (wave >> 1)]);
-        lds_flag_wait(&L.spost[1 + 0]);
-        lds_flag_wait(&L.spost[1 + 3]);
-        if constexpr (kWave2Adds) lds_flag_wait(&L.spost[1 + 2]);
-        if constexpr (kWave1Adds) lds_flag_wait(&L.spost[1 + 1]);
-        TrioPt A;
-        trio_sum_partials<kWave2Adds, kWave1Adds>(A, L, tl, T);
-        trio_store(gbuf, A, lane);
-    } else {  // S = k1 R' + k2 phi(R') for the partner, and its X K, Z K here
+    } else if (chain == 0) {  // S = k1 R' + k2 phi(R') for the partner, and its X K, Z K here
         TrioPt P1;
         lds_flag_wait(&L.spost[5 + (wave >> 1)]);
         trio_load(P1, xbuf, lane);
         trio_add(acc, acc, P1, T);
         trio_store(xbuf, acc, lane);
         fe26 zc, w, K;
-        lds_flag_wait(&L.spost[1 + 2]);  // w is wave 2's (stored before its comb partial)
+        lds_flag_wait(&L.spost[2]);  // w is the root helper's
         load_zc_w(zc, w);
         fe26_sqr(K, zc);
         fe26_mul(K, K, w);
         trio_scale_xz(SE, acc, K, T);
     }
-    __syncthreads();  // every wave is past phase C and phase A; S and T are in LDS
+    __syncthreads();  // every wave is past phase C and every helper past its last store; S and T are in LDS
     const uint32_t rfl = L.rflag[tl];
     if (chain == 0) {
         TrioPt G;
-        trio_load(G, gbuf, lane);
+        load_g(G);
         fe26 Z3;
         trio_add_z(Z3, G, SE, T);
         COOP_T(4);
         fe z, zi;
         fe26_to_fe(z, Z3);
-        FieldInv<FieldK1>::inv_pipe(zi, z);  // (on one wave: its partner is busy with the root's tail)
+        FieldInv<FieldK1>::inv_pipe(zi, z);  // (on one wave: its partner is busy with the last addition)
         COOP_T(5);
         fe26 zi26;
         fe26_from_fe(zi26, zi);
         fe26_sqr(zi2, zi26);
         fe26_mul(zi3, zi2, zi26);
-    } else {
+    } else if (chain == 1) {
         TrioPt S, G;
         trio_load(S, xbuf, lane);
-        trio_load(G, gbuf, lane);
-        fe26 y, ny, t, zc, w, K, l;
+        load_g(G);
+        fe26 y, zc, w, K, l;
         load_zc_w(zc, w);
         fe26_sqr(K, zc);
         fe26_mul(K, K, w);
-        trio_scale_xz(SE, S, K, T);  // (before the tail: less work between y and the hand-over)
-        {
-            fe26 st[kLive];
+        trio_scale_xz(SE, S, K, T);
 #pragma unroll
-            for (int j = 0; j < kLive; ++j) {
-#pragma unroll
-                for (int q = 0; q < 10; ++q) st[j].v[q] = L.sq[j][q][tl];
-                F26_SETM(st[j], 1);
-            }
-            fe26_sqrt_tail<0>(y, st);
-        }
-        fe26_sqr(t, y);
-        fe26_sub<3>(t, t, w);
-        const bool on = fe26_is_zero(t);  // y^2 = w: r is the x of a curve point
-        fe26_normalize(y);
-        fe26_neg<2>(ny, y);
-        fe26_normalize(ny);
-        fe26_cmov(y, ny, (y.v[0] & 1u) != ((rfl >> 4) & 1u));
+        for (int q = 0; q < 10; ++q) y.v[q] = L.sq[1][q][tl];
+        F26_SETM(y, 1);
         COOP_T(4);
         fe26_mul(l, zc, y);
         trio_scale_y(SE, l, T);
         trio_add(S, G, SE, T);  // T first: S_E = T doubles T, which holds no y
         trio_store(xbuf, S, lane);
-        if (seat.real) L.yok[tl] = on ? 1u : 0u;
         COOP_T(5);
     }
-    __syncthreads();  // X3, Y3 and the verdicts are in LDS
+    __syncthreads();  // X3, Y3 are in LDS
     if (chain == 0) {
         TrioPt O;
         trio_load(O, xbuf, lane);
@@ -1842,9 +2008,11 @@ __global__ __launch_bounds__(256, 1) void tx_verify_coop26_kernel(IO io, uint64_
     coop26_body(io, n, tab);
 }
 
-// Bit-identical to tx_verify_kernel<0, *>.
+// Bit-identical to tx_verify_kernel<0, *>.  kTrioRecoverThreads threads: four chain waves and four helpers, two
+// waves per SIMD (the second __launch_bounds__ argument counts waves per SIMD), so 256 VGPRs a wave.
+constexpr int kTrioRecoverThreads = 512;
 template <class IO>
-__global__ __launch_bounds__(256, 1) void tx_verify_trio26_kernel(IO io, uint64_t n, const uint32_t* __restrict__ tab,
+__global__ __launch_bounds__(kTrioRecoverThreads, 2) void tx_verify_trio26_kernel(IO io, uint64_t n, const uint32_t* __restrict__ tab,
                                                                   int tab_bits) {
     trio26_recover_body(io, n, tab, tab_bits);
 }
@@ -1882,8 +2050,8 @@ int launch_verify_small_secp(const TxKernelPolicy& pol, const IO& io, uint64_t n
         int bits = 8;
         const int rw = tables(&wk1, &wsm2, &bits);
         if (rw) return rw;
-        hipLaunchKernelGGL(tx_verify_trio26_kernel<IO>, dim3(static_cast<unsigned>((n + 39) / 40)), dim3(256), 0, st, io,
-                           n, wk1, bits);
+        hipLaunchKernelGGL(tx_verify_trio26_kernel<IO>, dim3(static_cast<unsigned>((n + 39) / 40)),
+                           dim3(kTrioRecoverThreads), 0, st, io, n, wk1, bits);
     } else if (pol.coop && pol.f26) {
         hipLaunchKernelGGL(tx_verify_coop26_kernel<IO>, grid, dim3(256), 0, st, io, n, k1);
     } else if constexpr (std::is_same_v<IO, TxIO>) {

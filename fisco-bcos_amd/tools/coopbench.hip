@@ -1,6 +1,8 @@
 // coopbench.hip -- phase timestamps (s_memtime cycles) of tx_verify_coop_kernel's (argv[1] = 26:
 // tx_verify_coop26_kernel's, trio: tx_verify_trio26_kernel's) workgroup 0 on a
 // 10k-tx batch of random inputs (the schedule is input-independent), to see where C2's latency goes.
+// trio prints eight waves (0..3 the chains, 4..7 the helpers): table / r^-1 / scalars posted, chain start and
+// phase C per chain wave, the Z^-1, each helper's last result posted, kernel end.
 #define BCOSGPU_COOP_TIMING 1
 #include "../csrc/ecc_tables.hip"
 #include "../csrc/ecc_coop.hip"
@@ -44,7 +46,8 @@ int main(int argc, char** argv) {
             const uint32_t *w1, *w2;
             int bits = 8;
             tables(&w1, &w2, &bits);
-            hipLaunchKernelGGL(tx_verify_trio26_kernel<TxIO>, dim3((n + 39) / 40), dim3(256), 0, 0, io, n, w1, bits);
+            hipLaunchKernelGGL(tx_verify_trio26_kernel<TxIO>, dim3((n + 39) / 40), dim3(kTrioRecoverThreads), 0, 0, io, n, w1,
+                               bits);
         } else if (f26)
             hipLaunchKernelGGL(tx_verify_coop26_kernel<TxIO>, dim3((n + 63) / 64), dim3(256), 0, 0, io, n, k1);
         else
@@ -52,8 +55,30 @@ int main(int argc, char** argv) {
                                dsn, dst);
         hipDeviceSynchronize();
     }
-    uint64_t t[4][8];
+    uint64_t t[8][12];
     hipMemcpyFromSymbol(t, HIP_SYMBOL(g_coop_t), sizeof(t));
+    if (trio) {
+        // eight waves (0..3 the chains, 4..7 the helpers), all stamps since wave 0's start; 0 = not stamped
+        // (signed: a wave can start a few cycles before wave 0)
+        const auto at = [&](int w, int k) { return t[w][k] ? (long long)(t[w][k] - t[0][0]) : 0ll; };
+        printf("{\"trio_stamps_since_wave0_start\": {");
+        for (int w = 0; w < 8; ++w) {
+            printf("%s\"wave%d\": {\"start\": %lld, \"phase_a_work_end\": %lld", w ? ", " : "", w, at(w, 0), at(w, 1));
+            if (w == 0) printf(", \"rinv_posted\": %lld, \"scalars_posted\": %lld", at(w, 7), at(w, 8));
+            if (w == 1) printf(", \"table_posted\": %lld", at(w, 6));
+            if (w < 4)
+                printf(", \"chain_start\": %lld, \"phase_c_end\": %lld, \"phase_c\": %lld, \"phase_d_4\": %lld, "
+                       "\"phase_d_5\": %lld",
+                       at(w, 9), at(w, 2), at(w, 2) - at(w, 9), at(w, 4), at(w, 5));
+            if (w == 6) printf(", \"root_posted\": %lld", at(w, 6));
+            if (w == 7) printf(", \"digest_posted\": %lld", at(w, 7));
+            if (w >= 4) printf(", \"last_result_posted\": %lld", at(w, 10));
+            printf(", \"kernel_end\": %lld}", at(w, 3));
+        }
+        printf("}, \"probes\": \"waves 0 / 2: phase_d_4 / 5 = start / end of Z^-1; waves 1 / 3: y loaded / the last "
+               "addition stored\"}\n");
+        return 0;
+    }
     printf("{\"cycles_since_start\": {");
     for (int w = 0; w < 4; ++w)
         printf("%s\"wave%d\": [%llu, %llu, %llu]", w ? ", " : "", w, (unsigned long long)(t[w][1] - t[w][0]),
