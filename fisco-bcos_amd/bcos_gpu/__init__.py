@@ -8,6 +8,7 @@ from .crypto import (SM3, CryptoSuite, Hash, InvalidSignature, Keccak256, Merkle
                      Secp256k1Crypto, calculate_merkle_proof_root, pack_messages, right160,
                      secp256k1_suite, sm_suite)
 from . import tars
+from . import txpool
 from .cipher import decrypt_values, encrypt_values
 from .header import (BlockHeader, ConsensusSet, HeaderSignature, check_headers, header_hashes, pack_headers)
 from .pbft import PBFTMessage, PrecommitProof, check_messages

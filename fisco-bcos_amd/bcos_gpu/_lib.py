@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libbcosgpu.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "bcos_gpu.h")
 
-OK, E_ARG, E_HIP, E_NODEV, E_EMPTY = 0, -1, -2, -3, -4
+OK, E_ARG, E_HIP, E_NODEV, E_EMPTY, E_ENGINE = 0, -1, -2, -3, -4, -5
 WEDPR_ENGINE_ERROR = -2
 KECCAK256, SM3 = 0, 1
 SUITE_SECP256K1, SUITE_SM2 = 0, 1
@@ -106,6 +106,15 @@ _SIGS = {
     "bcosgpu_tars_tx_verify_batch": (_I, [_I, _P, _P, _SZ, _I, _I, _P, _P, _P]),
     "bcosgpu_tars_tx_verify_batch_dev": (_I, [_I, _P, _P, _SZ, _I, _I, _P, _P, _P, _P, _P, ctypes.c_uint64, _P, _P,
                                               _P, _P]),
+    "bcosgpu_txpool_create": (_I, [_I, _I, _U8P, _SZ, _U8P, _SZ, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64, _P]),
+    "bcosgpu_txpool_destroy": (_I, [_P]),
+    "bcosgpu_txpool_admit": (_I, [_P, _I, _P, _P, _SZ, _P, _P, _P, _P]),
+    "bcosgpu_txpool_admit_dev": (_I, [_P, _I, _P, _P, _SZ, ctypes.c_uint64, _P, _P, _P, _P]),
+    "bcosgpu_txpool_block_committed": (_I, [_P, ctypes.c_int64, _P, _SZ, _P, _SZ]),
+    "bcosgpu_txpool_remove": (_I, [_P, _P, _SZ, _P, _SZ]),
+    "bcosgpu_txpool_load_ledger_nonces": (_I, [_P, _P, _P, _P, _SZ]),
+    "bcosgpu_txpool_info": (_I, [_P, _P]),
+    "bcosgpu_txpool_dump": (_I, [_P, _I, _P, ctypes.c_uint64, _P]),
     "bcosgpu_secp256k1_recover": (_I, [_I, _P, _P, _SZ, _P]),
     "bcosgpu_secp256k1_verify": (_I, [_I, _P, _P, _P, _SZ]),
     "bcosgpu_sm2_verify": (_I, [_I, _P, _P, _P]),

@@ -231,3 +231,19 @@ def tars_tx_verify(suite, enc, enc_off, pre, pre_off, sig, sig_off, work, txhash
                                                  _p(pre_off), _p(sig), _p(sig_off), _p(work),
                                                  work.numel() * work.element_size(), _p(txhash), _p(sender),
                                                  _p(status), _s(stream)))
+
+
+TXPOOL_FULL, TXPOOL_PROPOSAL = 0, 1
+
+
+def txpool_admit(pool, enc, enc_off, txhash, sender, nonce, status, mode=TXPOOL_FULL):
+    """Stateful admission of n Tars-encoded transactions over device tensors (bcosgpu_txpool_admit_dev): `pool` a
+    bcos_gpu.txpool.Pool; enc uint8[B], enc_off int64[n+1], txhash uint8[n,32], sender uint8[n,20], nonce
+    uint8[n,32], status int32[n].  Runs on the pool's own stream: this waits for torch's current stream first,
+    and the outputs are complete when it returns."""
+    _dev(enc)
+    n = enc_off.numel() - 1
+    assert status.element_size() == 4 and enc.numel() < 2 ** 63
+    torch.cuda.current_stream().synchronize()
+    check(lib().bcosgpu_txpool_admit_dev(pool.handle, mode, _p(enc), _p(enc_off), n, enc.numel(), _p(txhash),
+                                         _p(sender), _p(nonce), _p(status)))

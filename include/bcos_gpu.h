@@ -273,6 +273,78 @@ int bcosgpu_tars_tx_verify_batch_dev(int suite, const uint8_t* d_enc, const uint
                                      uint64_t* d_sig_off, void* d_work, uint64_t work_bytes, uint8_t* d_txhash32,
                                      uint8_t* d_sender20, uint8_t* d_status, void* stream);
 
+/* ---------------------------------------------------------------- transaction admission with the pool's state */
+/* The checks the batch sites make around Transaction::verify, against state that lives in HBM across calls:
+ *   MemoryStorage::verifyAndSubmitTransaction  bcos-txpool/bcos-txpool/txpool/storage/MemoryStorage.cpp:223-273
+ *       (under batchImportTxs), with TxValidator::verify  .../txpool/validator/TxValidator.cpp:27-69,
+ *       TxPoolNonceChecker::checkNonce  .../validator/TxPoolNonceChecker.cpp:34-49 and
+ *       LedgerNonceChecker::checkNonce / checkBlockLimit / batchInsert  .../validator/LedgerNonceChecker.cpp:36-99
+ *   MemoryStorage::enforceSubmitTransaction    MemoryStorage.cpp:147-221 (importDownloadedTxs with a proposal)
+ *   MemoryStorage::batchRemove                 MemoryStorage.cpp:435-498, and removeInvalidTxs
+ * A pool owns three sets of 32-byte keys, each a strictly ascending array (ascending as a big-endian 256-bit
+ * number) with a device-side count: the pool's tx hashes (m_txsTable's keys), the pool's nonces, the ledger's
+ * nonces of the last block_limit_range blocks; plus the per-block nonce lists of
+ * LedgerNonceChecker::m_blockNonceCache (host copies), chain id, group id, block_limit_range and the current block
+ * number.  A nonce is TransactionImpl::nonce()'s u256 (TransactionImpl.cpp:62-68) as a 32-byte big-endian key;
+ * only canonical strings are parsed (empty, or 1..78 digits without a leading 0 unless "0", below 2^256): any
+ * other transaction gets status 4 and is left to the host's own code.
+ * One mutex and one stream per pool: calls on one pool are serialised, every call returns after its work on the
+ * pool's stream has finished, and an error return leaves nothing of the call running.  n == 0 is BCOSGPU_OK and
+ * changes nothing.  A kernel that would store outside a buffer skips the store and sets the pool's error word;
+ * the call then returns BCOSGPU_E_ENGINE, and so does every later call on that pool except info and destroy. */
+#define BCOSGPU_E_ENGINE (-5) /* the pool's error word is set (see bcosgpu_txpool_info) */
+typedef struct bcosgpu_txpool bcosgpu_txpool;
+#define BCOSGPU_TXPOOL_FULL 0     /* batchImportTxs: every check, the batch judged in index order */
+#define BCOSGPU_TXPOOL_PROPOSAL 1 /* enforceSubmitTransaction: decode, nonce against the ledger, signature */
+#define BCOSGPU_TXPOOL_HASHES 0
+#define BCOSGPU_TXPOOL_NONCES 1
+#define BCOSGPU_TXPOOL_LEDGER 2
+/* per-transaction status (uint32): 0 accepted, 2 the decode throws, 4 nonce string not canonical, and
+ * TransactionStatus (bcos-protocol/TransactionStatus.h): 10000 NonceCheckFail, 10001 BlockLimitCheckFail,
+ * 10004 AlreadyInTxPool, 10006 InvalidChainId, 10007 InvalidGroupId, 10008 InvalidSignature */
+/* initial_capacity: keys per set before the first growth (0 = 4096); sets grow by at least doubling, between
+ * calls.  0 <= block_number, block_limit_range <= 2^62. */
+int bcosgpu_txpool_create(int device, int suite, const char* chain_id, size_t chain_len, const char* group_id,
+                          size_t group_len, int64_t block_limit_range, int64_t block_number, uint64_t initial_capacity,
+                          bcosgpu_txpool** out);
+int bcosgpu_txpool_destroy(bcosgpu_txpool* pool);
+/* Decode + verify n Tars-encoded transactions as the device call above does with check_sig on and check_hash
+ * off, then judge them.  FULL: in the order hash in the pool (10004), group (10007), chain (10006), nonce not
+ * canonical (4), nonce in the pool (10000), nonce in the ledger (10000), block limit (number >= limit or number +
+ * range < limit: 10001), signature (10008), as if one after another: an accepted transaction's nonce and hash are in
+ * the sets when the next one is judged.  PROPOSAL: 2, 4, 10000 (ledger only), 10008 or 0, no rule between the
+ * transactions of the batch; the accepted hashes enter the pool's table.
+ * Outputs per transaction: txhash32 (zero when the decode throws), sender20 (zero unless status 0), nonce32 (zero
+ * unless canonical), status. */
+int bcosgpu_txpool_admit(bcosgpu_txpool* pool, int mode, const uint8_t* enc, const uint64_t* enc_off, size_t n,
+                         uint8_t* txhash32, uint8_t* sender20, uint8_t* nonce32, uint32_t* status);
+/* The same over device buffers (enc_bytes: the readable bytes at d_enc, at least d_enc_off[n]; d_status 4-byte
+ * aligned).  Runs on the pool's stream: the inputs must be complete before the call, the outputs are complete when
+ * it returns. */
+int bcosgpu_txpool_admit_dev(bcosgpu_txpool* pool, int mode, const uint8_t* d_enc, const uint64_t* d_enc_off, size_t n,
+                             uint64_t enc_bytes, uint8_t* d_txhash32, uint8_t* d_sender20, uint8_t* d_nonce32,
+                             uint32_t* d_status);
+/* A block went to the ledger (batchRemove + LedgerNonceChecker::batchInsert; host pointers, duplicates allowed):
+ * hashes -= txhashes; the pool's block number advances to `number`; ledger += nonces; nonces -= nonces; the list
+ * is remembered under `number` unless that number already has one; block number - block_limit_range expires:
+ * ledger -= its remembered list. */
+int bcosgpu_txpool_block_committed(bcosgpu_txpool* pool, int64_t number, const uint8_t* txhashes32, size_t nhashes,
+                                   const uint8_t* nonces32, size_t nnonces);
+/* removeInvalidTxs: hashes -= txhashes, nonces -= nonces. */
+int bcosgpu_txpool_remove(bcosgpu_txpool* pool, const uint8_t* txhashes32, size_t nhashes, const uint8_t* nonces32,
+                          size_t nnonces);
+/* LedgerNonceChecker::initNonceCache (:26-34): block b's nonces are nonces32[32 nonce_off[b] .. 32 nonce_off[b+1]);
+ * every list is remembered (replacing an earlier one of that number), every nonce enters the ledger set. */
+int bcosgpu_txpool_load_ledger_nonces(bcosgpu_txpool* pool, const int64_t* numbers, const uint64_t* nonce_off,
+                                      const uint8_t* nonces32, size_t nblocks);
+/* out: counts of hashes / nonces / ledger, their capacities, the block number, the remembered blocks, the error
+ * word (0 = no kernel ever refused a store or a count). */
+#define BCOSGPU_TXPOOL_INFO_WORDS 9
+int bcosgpu_txpool_info(bcosgpu_txpool* pool, uint64_t out[BCOSGPU_TXPOOL_INFO_WORDS]);
+/* A set's keys in ascending order (tests, diagnosis): *count receives the set's count; keys32 must hold it
+ * (capacity in keys), else BCOSGPU_E_ARG. */
+int bcosgpu_txpool_dump(bcosgpu_txpool* pool, int which, uint8_t* keys32, uint64_t capacity, uint64_t* count);
+
 /* ---------------------------------------------------------------- host-side preimage packer */
 /* A view of bcostars::TransactionData (bcos-tars-protocol/.../tars/Transaction.tars:2-11): pointers
  * into the caller's decoded transaction, nothing is copied until packing. */

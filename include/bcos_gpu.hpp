@@ -434,5 +434,87 @@ inline std::pair<bool, bytes> ecRecover(const uint8_t* in, size_t len) {
     return {true, bytes(out, out + 32)};
 }
 
+/* The transaction pool's admission state on the GPU (bcosgpu_txpool_*): the handle owned, the calls as members.
+ * What replaces what: INTEGRATION.md, "Transaction admission with the pool's state".  A nonce is the 32-byte
+ * big-endian form of TransactionImpl::nonce()'s u256. */
+struct TxAdmission {
+    std::vector<HashType> hashes;
+    std::vector<std::array<uint8_t, 20>> senders;
+    std::vector<HashType> nonces;
+    std::vector<uint32_t> status;  // 0 accepted, 2, 4 or a TransactionStatus (bcos_gpu.h)
+};
+struct TxPoolInfo {
+    uint64_t hashes, nonces, ledger, hashesCapacity, noncesCapacity, ledgerCapacity, blockNumber, blocks, errorWord;
+};
+class GpuTxPool {
+public:
+    GpuTxPool(int suite, std::string_view chainId, std::string_view groupId, int64_t blockLimitRange,
+              int64_t blockNumber = 0, uint64_t initialCapacity = 0, int device = 0) {
+        check(bcosgpu_txpool_create(device, suite, chainId.data(), chainId.size(), groupId.data(), groupId.size(),
+                                    blockLimitRange, blockNumber, initialCapacity, &pool_));
+    }
+    ~GpuTxPool() { bcosgpu_txpool_destroy(pool_); }
+    GpuTxPool(const GpuTxPool&) = delete;
+    GpuTxPool& operator=(const GpuTxPool&) = delete;
+
+    /* batchImportTxs (BCOSGPU_TXPOOL_FULL) / importDownloadedTxs with a proposal (BCOSGPU_TXPOOL_PROPOSAL) over
+     * encoded transactions */
+    TxAdmission admit(const std::vector<std::string_view>& encoded, int mode = BCOSGPU_TXPOOL_FULL) {
+        const size_t n = encoded.size();
+        TxAdmission r{std::vector<HashType>(n, HashType{}), std::vector<std::array<uint8_t, 20>>(n), std::vector<HashType>(n, HashType{}),
+                      std::vector<uint32_t>(n, 0)};
+        if (n == 0) return r;
+        std::vector<uint64_t> off(n + 1, 0);
+        bytes data;
+        for (size_t i = 0; i < n; ++i) {
+            data.insert(data.end(), encoded[i].begin(), encoded[i].end());
+            off[i + 1] = data.size();
+        }
+        data.push_back(0);
+        check(bcosgpu_txpool_admit(pool_, mode, data.data(), off.data(), n, r.hashes[0].data(), r.senders[0].data(),
+                                   r.nonces[0].data(), r.status.data()));
+        return r;
+    }
+    /* MemoryStorage::batchRemove + LedgerNonceChecker::batchInsert */
+    void blockCommitted(int64_t number, const std::vector<HashType>& txHashes, const std::vector<HashType>& nonces) {
+        check(bcosgpu_txpool_block_committed(pool_, number, flat(txHashes), txHashes.size(), flat(nonces), nonces.size()));
+    }
+    /* removeInvalidTxs */
+    void remove(const std::vector<HashType>& txHashes, const std::vector<HashType>& nonces) {
+        check(bcosgpu_txpool_remove(pool_, flat(txHashes), txHashes.size(), flat(nonces), nonces.size()));
+    }
+    /* LedgerNonceChecker::initNonceCache */
+    void loadLedgerNonces(const std::vector<std::pair<int64_t, std::vector<HashType>>>& blocks) {
+        std::vector<int64_t> numbers;
+        std::vector<uint64_t> off{0};
+        std::vector<HashType> all;
+        for (const auto& b : blocks) {
+            numbers.push_back(b.first);
+            all.insert(all.end(), b.second.begin(), b.second.end());
+            off.push_back(all.size());
+        }
+        check(bcosgpu_txpool_load_ledger_nonces(pool_, numbers.data(), off.data(), flat(all), blocks.size()));
+    }
+    TxPoolInfo info() const {
+        uint64_t w[BCOSGPU_TXPOOL_INFO_WORDS] = {};
+        check(bcosgpu_txpool_info(pool_, w));
+        return TxPoolInfo{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8]};
+    }
+    /* the keys of BCOSGPU_TXPOOL_HASHES / _NONCES / _LEDGER in ascending order */
+    std::vector<HashType> dump(int which) const {
+        if (which < 0 || which > 2) throw std::invalid_argument("bcosgpu: bad set");
+        uint64_t n = 0, w[BCOSGPU_TXPOOL_INFO_WORDS] = {};
+        check(bcosgpu_txpool_info(pool_, w));
+        std::vector<HashType> keys(std::max<uint64_t>(1, w[which]));
+        check(bcosgpu_txpool_dump(pool_, which, keys[0].data(), keys.size(), &n));
+        keys.resize(n);
+        return keys;
+    }
+
+private:
+    static const uint8_t* flat(const std::vector<HashType>& v) { return v.empty() ? nullptr : v[0].data(); }
+    bcosgpu_txpool* pool_ = nullptr;
+};
+
 }  // namespace bcosgpu
 #endif
