@@ -10,6 +10,7 @@
 #include "../../include/bcos_gpu.h"
 #include "host_rt.h"
 #include "cipher_host.h"
+#include "coalesce_queue.h"
 
 namespace bcosgpu {
 
@@ -158,31 +159,7 @@ int launch_pbft_check(int suite, const PbftCheckArgs& a, hipStream_t st);
 
 // coalesce.hip: the host-pointer signature calls as jobs of a per-device queue, coalesced into shared
 // launches (see the file header).  coalesced_run blocks until the job's results are written.
-enum SigJobKind { kSigJobRecoverK1 = 0, kSigJobVerifySM2 = 1, kSigJobVerifyK1 = 2, kSigJobKinds = 3 };
-struct SigJob {
-    int kind = 0;
-    size_t n = 0;
-    const uint8_t* hash32 = nullptr;  // n x 32
-    const uint8_t* sig = nullptr;     // item i at sig + sig_stride * i: r||s||v (recover), r||s[||pub] (verify)
-    size_t sig_stride = 0;
-    const uint8_t* pub64 = nullptr;   // verify: the known keys (SM2: null = the key is sig[64..128))
-    uint8_t* out_pub64 = nullptr;     // recover only, nullable
-    uint8_t* out_addr20 = nullptr;    // recover / SM2 verify, nullable
-    uint8_t* out_ok = nullptr;        // n bytes: 1 valid, 0 invalid
-    int rc = 0;                       // filled in by the engine: 0 or BCOSGPU_E_*, with err
-    std::string err;
-    bool queued = false, woken = false;  // under the device queue's mutex
-    uint64_t seq = 0;                    // arrival order in its device queue
-    int64_t t_enq = 0;                   // steady-clock ns: queued (coalescer statistics)
-    std::atomic<int64_t> t_notify{0};    // ... last notified
-    std::atomic<uint32_t> wake{0};       // the owner's futex word: bit 0 woken to lead, bit 1 done (coalesce.hip)
-    SigJob* next = nullptr;              // the device queue's lock-free arrival stack
-};
-// (an aggregate: the engine's fields keep their defaults)
-inline SigJob sig_job(int kind, size_t n, const uint8_t* hash32, const uint8_t* sig, size_t sig_stride,
-                      const uint8_t* pub64, uint8_t* out_pub64, uint8_t* out_addr20, uint8_t* out_ok) {
-    return SigJob{kind, n, hash32, sig, sig_stride, pub64, out_pub64, out_addr20, out_ok};
-}
+// The job and the queue protocol are coalesce_queue.h's (host-only, tested without a GPU).
 int coalesced_run(int device, SigJob& job);
 int coalesce_stats(int device, uint64_t* out, int n, int reset);
 
