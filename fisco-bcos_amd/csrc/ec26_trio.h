@@ -25,6 +25,7 @@
 // and Zs = Z on lane 2 (lanes 0 and 1 hold don't-care values there), inf on every lane.  Magnitudes:
 // dbl -> (10, 10, 2), madd -> (9, 6, 2), as CurveK1x.
 #pragma once
+#include <type_traits>
 #include "ec26.h"
 
 #ifndef TRIO_DUMP  // tools/triobench.hip defines it to dump the addition's per-level values
@@ -798,6 +799,304 @@ F26_HD void trio_add_z(fe26& Z3, const TrioPt& P, const TrioPt& Q, const TrioLan
     }
     fe26_cmov(Z3, Q.Zs, P.inf);
     fe26_cmov(Z3, P.Zs, !P.inf && Q.inf);
+}
+
+// ------------------------------------------------------------------ the recovery kernel's table on three waves
+// trio_table_shared: the co-Z table of P (1 P .. 8 P over one Z, beta x of each entry, that Z, and K = Zc^2 w)
+// built by three waves of one workgroup, one lane per tx, each wave one ROLE.  Every stored word is what the
+// one-wave build (trio_table_staged, below) stores: the multiples come from the same calls on the same
+// inputs, and the rescale factors s_j = Zc / Z_j are the same field values (only the order of the products
+// differs, and every stored value is canonical).
+//   kTableLong    2P, 3P, 6P, 7P; then the suffix products suf_j = Z_j .. Z_7 (j = 7 .. 2); entries 1, 2, 3
+//   kTablePrefix  no multiple; the prefix products pre_j = Z_1 .. Z_j (j = 1 .. 6) as the Z_j arrive, Zc, K;
+//                 entries 0 and 7
+//   kTableShort   4P, 5P, 8P from the long wave's 2P; entries 4, 5, 6
+// LDS (a struct with the members of Trio26RecoverLds named here): the Jacobian multiple (j + 1) P waits in
+// L.tab[j] (X, Y raw limbs, m 10) and L.tabphx[j] (Z, m 2) until entry j replaces it; pre_1 .. pre_5 wait in
+// the rows of L.xg (free before phase D; pre_6 stays in the prefix wave's registers), suf_2 .. suf_7 in L.tsuf,
+// raw limbs of magnitude <= 2.
+// H is the hand-off: post(slot) is a release store of 1 by the wave, wait(slot) acquire loads until it reads
+// non-zero (device: lds_flag_post / lds_flag_wait on L.spost; host test: std::atomic), stamp(k) a probe.
+//   slot             posted by   after                          waited for by
+//   kTfMul0 + j      long/short  the multiple (j + 1) P stored  prefix (all), long (7, 6, .. 2), short (1)
+//   kTfPre           prefix      its last read of a Z_j; pre_j, zc  long, short
+//   kTfSuf           long        its last read of a Z_j; suf_j  prefix, short
+//   kTfDone[role]    each role   its last entry (prefix: and K) the chains
+// An entry's stores overwrite row j, so they follow every other wave's last read of it: every entry 1 .. 7 is
+// stored behind kTfPre and kTfSuf (a wave's own flag is its program order), and the short wave's read of 2P
+// precedes its post of kTfMul0 + 7, which the long wave waits for.  Row 0 holds no multiple.  No wait has a
+// cycle: the long wave's multiples wait for nothing, the short wave's for kTfMul0 + 1 only, kTfPre and kTfSuf
+// for multiples only.  Control flow does not depend on the lane's values, so rejected and idle lanes run the
+// same flag sequence.
+constexpr int kTableLong = 0, kTablePrefix = 1, kTableShort = 2;
+constexpr int kTfDone[3] = {1, 3, 4};  // Trio26RecoverLds::spost slots
+constexpr int kTfPre = 7, kTfSuf = 8;
+constexpr int kTfMul0 = 8;  // the multiples' slots are kTfMul0 + j, j = 1 .. 7 (slot 8 itself is kTfSuf's)
+constexpr int kTfSlots = 16;
+
+namespace trio_table {
+// compile-time loop I .. N - 1 (the entries and flag slots are constants); ecc_device.h's Unroll is device-only,
+// and this header compiles on the host
+template <int I, int N>
+struct Seq {
+    template <class Fn>
+    F26_HD static void run(Fn&& fn) {
+        if constexpr (I < N) {
+            fn(std::integral_constant<int, I>{});
+            Seq<I + 1, N>::run(fn);
+        }
+    }
+};
+template <class LDS>
+F26_HD void put(LDS& L, int j, const Jac26& J, int lane) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        L.tab[j][q][lane] = J.X.v[q];
+        L.tab[j][10 + q][lane] = J.Y.v[q];
+        L.tabphx[j][q][lane] = J.Z.v[q];
+    }
+}
+template <class LDS>
+F26_HD void get_z(fe26& Z, const LDS& L, int j, int lane) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) Z.v[q] = L.tabphx[j][q][lane];
+    F26_SETM(Z, 2);
+}
+template <class LDS>
+F26_HD void get_xy(fe26& X, fe26& Y, const LDS& L, int j, int lane) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        X.v[q] = L.tab[j][q][lane];
+        Y.v[q] = L.tab[j][10 + q][lane];
+    }
+    F26_SETM(X, 10);
+    F26_SETM(Y, 10);
+}
+// a product (m 1; pre_1 and suf_7 are a Z itself, m 2) parked as raw limbs: rows 10 i .. 10 i + 9 of `rows`
+// (row number -> that row's 64 words)
+template <class Rows>
+F26_HD void park(const Rows& rows, int i, const fe26& a, int lane) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) rows(10 * i + q)[lane] = a.v[q];
+}
+template <class Rows>
+F26_HD void unpark(fe26& a, const Rows& rows, int i, int lane) {
+#pragma unroll
+    for (int q = 0; q < 10; ++q) a.v[q] = rows(10 * i + q)[lane];
+    F26_SETM(a, 2);
+}
+F26_HD void store_canonical(uint32_t (*dst)[64], const fe26& a, int lane) {
+    fe26 t;
+    fe26_copy(t, a);
+    fe26_normalize(t);
+#pragma unroll
+    for (int q = 0; q < 10; ++q) dst[q][lane] = t.v[q];
+}
+// entry j from its multiple (X, Y) and s = Zc / Z_j: (X s^2, Y s^3) and beta X s^2, canonical limbs
+template <class LDS>
+F26_HD void entry(LDS& L, int j, const fe26& s, const fe26& X, const fe26& Y, const fe26& beta, int lane) {
+    fe26 s2, s3, x, y, bx;
+    fe26_sqr(s2, s);
+    fe26_mul(s3, s2, s);
+    fe26_mul(x, X, s2);
+    fe26_mul(y, Y, s3);
+    fe26_mul(bx, x, beta);
+    store_canonical(L.tab[j], x, lane);
+    store_canonical(L.tab[j] + 10, y, lane);
+    store_canonical(L.tabphx[j], bx, lane);
+}
+}  // namespace trio_table
+
+// The one-wave build, the reference of trio_table_shared (tests/cpp/trio_table_test.cpp; no kernel calls it):
+// the multiples in the order of multiples8_26, parked in the table's own rows of column `lane`, then s_j from
+// prefix products and a running suffix, the entries from the top down (coz_table26), beta x, Zc and K.
+template <class LDS>
+F26_HD void trio_table_staged(LDS& L, const Aff26& P, const fe26& w, const fe26& beta, int lane) {
+    using namespace trio_table;
+    {
+        Jac26 A, B, N;  // T[j] = (j + 1) P
+        CurveK1x::from_aff(B, P);
+        CurveK1x::dbl(A, B);      // 2 P
+        put(L, 1, A, lane);
+        CurveK1x::madd(B, A, P);  // 3 P
+        put(L, 2, B, lane);
+        CurveK1x::dbl(N, A);      // 4 P
+        put(L, 3, N, lane);
+        CurveK1x::dbl(A, B);      // 6 P
+        put(L, 5, A, lane);
+        CurveK1x::madd(B, A, P);  // 7 P
+        put(L, 6, B, lane);
+        CurveK1x::madd(B, N, P);  // 5 P
+        put(L, 4, B, lane);
+        CurveK1x::dbl(A, N);      // 8 P
+        put(L, 7, A, lane);
+    }
+    fe26 pre[7], suf, Zc, Zj, K;
+    fe26_one(pre[0]);
+    get_z(pre[1], L, 1, lane);
+    Seq<2, 7>::run([&](auto J) {
+        get_z(Zj, L, J, lane);
+        fe26_mul(pre[J], pre[J - 1], Zj);
+    });
+    get_z(Zj, L, 7, lane);
+    fe26_mul(Zc, pre[6], Zj);
+    fe26_zero(suf);
+    Seq<0, 8>::run([&](auto J) {
+        constexpr int j = 7 - decltype(J)::value;
+        fe26 sj, s2, s3, X, Y, bx;
+        if constexpr (j == 0) {
+            fe26_copy(X, P.x);
+            fe26_copy(Y, P.y);
+        } else {
+            get_xy(X, Y, L, j, lane);
+            get_z(Zj, L, j, lane);
+        }
+        if constexpr (j == 7) fe26_copy(sj, pre[6]);
+        else if constexpr (j <= 1) fe26_copy(sj, suf);
+        else fe26_mul(sj, pre[j - 1], suf);
+        if constexpr (j == 7) fe26_copy(suf, Zj);
+        else if constexpr (j >= 1) fe26_mul(suf, suf, Zj);
+        fe26_sqr(s2, sj);
+        fe26_mul(s3, s2, sj);
+        fe26_mul(X, X, s2);
+        fe26_mul(Y, Y, s3);
+        fe26_mul(bx, X, beta);
+        store_canonical(L.tab[j], X, lane);
+        store_canonical(L.tab[j] + 10, Y, lane);
+        store_canonical(L.tabphx[j], bx, lane);
+    });
+    {
+        fe26 t;
+        uint32_t z8[8];
+        fe26_copy(t, Zc);
+        fe26_normalize(t);
+        fe26_to_words(z8, t);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) L.zc[q][lane] = z8[q];
+    }
+    fe26_sqr(K, Zc);
+    fe26_mul(K, K, w);
+    store_canonical(L.kw, K, lane);
+}
+
+// P = R' (m 1 both), w of magnitude <= 2 (the prefix role's K), beta the GLV constant; see above.
+template <int ROLE, class LDS, class H>
+F26_HD void trio_table_shared(LDS& L, H& h, const Aff26& P, const fe26& w, const fe26& beta, int lane) {
+    using namespace trio_table;
+    constexpr int kXgRows = sizeof(L.xg[0]) / sizeof(L.xg[0][0]);
+    static_assert(sizeof(L.xg) / sizeof(L.xg[0]) * kXgRows >= 50, "xg holds the five parked prefix products");
+    static_assert(sizeof(L.tsuf) / sizeof(L.tsuf[0][0]) >= 60, "tsuf holds the six suffix products");
+    const auto pre = [&](int r) -> uint32_t* { return L.xg[r / kXgRows][r % kXgRows]; };  // pre_j at place j - 1
+    const auto suf = [&](int r) -> uint32_t* { return L.tsuf[r / 10][r % 10]; };          // suf_j at place j - 2
+    fe26 X, Y, s, Zj;
+    if constexpr (ROLE == kTableLong) {
+        {
+            Jac26 A, B;
+            CurveK1x::from_aff(B, P);
+            CurveK1x::dbl(A, B);      // 2 P
+            put(L, 1, A, lane);
+            h.post(kTfMul0 + 1);
+            CurveK1x::madd(B, A, P);  // 3 P
+            put(L, 2, B, lane);
+            h.post(kTfMul0 + 2);
+            CurveK1x::dbl(A, B);      // 6 P
+            put(L, 5, A, lane);
+            h.post(kTfMul0 + 5);
+            CurveK1x::madd(B, A, P);  // 7 P
+            put(L, 6, B, lane);
+            h.post(kTfMul0 + 6);
+        }
+        h.stamp(10);
+        fe26 run, keep[3];  // suf_2 .. suf_4 stay here for this wave's entries
+        h.wait(kTfMul0 + 7);
+        get_z(run, L, 7, lane);
+        park(suf, 5, run, lane);
+        Seq<0, 5>::run([&](auto I) {
+            constexpr int j = 6 - decltype(I)::value;  // 6 .. 2
+            h.wait(kTfMul0 + j);
+            get_z(Zj, L, j, lane);
+            fe26_mul(run, run, Zj);
+            park(suf, j - 2, run, lane);
+            if constexpr (j <= 4) fe26_copy(keep[j - 2], run);
+        });
+        h.post(kTfSuf);
+        h.stamp(11);
+        h.wait(kTfPre);
+        get_xy(X, Y, L, 1, lane);
+        entry(L, 1, keep[0], X, Y, beta, lane);
+        Seq<2, 4>::run([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            unpark(s, pre, j - 2, lane);
+            fe26_mul(s, s, keep[j - 1]);
+            get_xy(X, Y, L, j, lane);
+            entry(L, j, s, X, Y, beta, lane);
+        });
+    } else if constexpr (ROLE == kTableShort) {
+        {
+            Jac26 A, B, N;
+            h.wait(kTfMul0 + 1);
+            get_xy(A.X, A.Y, L, 1, lane);
+            get_z(A.Z, L, 1, lane);
+            A.inf = false;            // 2 P of an affine P
+            CurveK1x::dbl(N, A);      // 4 P
+            put(L, 3, N, lane);
+            h.post(kTfMul0 + 3);
+            CurveK1x::madd(B, N, P);  // 5 P
+            put(L, 4, B, lane);
+            h.post(kTfMul0 + 4);
+            CurveK1x::dbl(A, N);      // 8 P
+            put(L, 7, A, lane);
+            h.post(kTfMul0 + 7);
+        }
+        h.stamp(10);
+        h.wait(kTfPre);
+        h.wait(kTfSuf);
+        Seq<4, 7>::run([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            fe26 t;
+            unpark(s, pre, j - 2, lane);
+            unpark(t, suf, j - 1, lane);
+            fe26_mul(s, s, t);
+            get_xy(X, Y, L, j, lane);
+            entry(L, j, s, X, Y, beta, lane);
+        });
+    } else {
+        static_assert(ROLE == kTablePrefix, "three roles");
+        fe26 run, Zc, K;
+        h.wait(kTfMul0 + 1);
+        get_z(run, L, 1, lane);
+        park(pre, 0, run, lane);
+        Seq<2, 7>::run([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            h.wait(kTfMul0 + j);
+            get_z(Zj, L, j, lane);
+            fe26_mul(run, run, Zj);
+            if constexpr (j < 6) park(pre, j - 1, run, lane);  // (pre_6 = s_7 is this wave's own)
+        });
+        h.wait(kTfMul0 + 7);
+        get_z(Zj, L, 7, lane);
+        fe26_mul(Zc, run, Zj);
+        {
+            fe26 t;
+            uint32_t z8[8];
+            fe26_copy(t, Zc);
+            fe26_normalize(t);
+            fe26_to_words(z8, t);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) L.zc[q][lane] = z8[q];
+        }
+        h.post(kTfPre);
+        h.stamp(10);
+        fe26_sqr(K, Zc);
+        fe26_mul(K, K, w);
+        store_canonical(L.kw, K, lane);
+        entry(L, 0, Zc, P.x, P.y, beta, lane);
+        h.wait(kTfSuf);
+        get_xy(X, Y, L, 7, lane);
+        entry(L, 7, run, X, Y, beta, lane);  // s_7 = pre_6
+    }
+    h.post(kTfDone[ROLE]);
+    h.stamp(6);
 }
 
 }  // namespace bcosgpu

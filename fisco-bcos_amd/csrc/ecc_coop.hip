@@ -1015,9 +1015,9 @@ struct Trio26Lds {
     uint32_t post[3];
 };
 struct Trio26RecoverLds : Trio26Lds {
-    // the square root, raw limbs: w = x^3 + 7 (0) and y (1, normalized, v's parity), from the root's helper
-    // to phase D; and its verdict y^2 = w
-    uint32_t sq[2][10][40];
+    // the square root y of w = x^3 + 7, raw limbs (normalized, v's parity), from the root's helper to phase D;
+    // and its verdict y^2 = w
+    uint32_t sq[10][40];
     uint32_t yok[64];
     // The kernel runs eight waves: 0..3 the chains (wave w: chain w & 1 of txs 20 (w >> 1) .. + 19), 4..7
     // the helpers (one lane per tx; helper h = wave - 4 shares a SIMD with wave h).  No barrier separates
@@ -1027,19 +1027,56 @@ struct Trio26RecoverLds : Trio26Lds {
     //   post[0]    wave 0                   helpers with comb windows    xrinv (r^-1 mod n)
     //   post[1]    helper 3                 helpers with comb windows    xe (the digest mod n)
     //   spost[0]   wave 0                   waves 0..3, before phase C   k, flags (the GLV halves of s / r)
-    //   spost[1]   wave 1                   waves 0..3, before phase C   tab, tabphx, zc (the table of R')
-    //   spost[2]   helper 2                 waves 0, 2, in phase D       sq, rflag, yok (w, y, the verdicts)
+    //   spost[1]   wave 1                   waves 0..3, before phase C   tab, tabphx of entries 1, 2, 3
+    //   spost[3]   wave 2                   waves 0..3, before phase C   entries 0 and 7, zc, kw (K = Zc^2 w)
+    //   spost[4]   wave 3                   waves 0..3, before phase C   entries 4, 5, 6
+    //   spost[7]   wave 2                   waves 1, 3, in the table     xg as the prefix products pre_1 .. pre_6;
+    //                                                                    wave 2's last read of a multiple's Z
+    //   spost[8]   wave 1                   waves 2, 3, in the table     tsuf (the suffix products suf_2 .. suf_7);
+    //                                                                    wave 1's last read of a multiple's Z
+    //   spost[8+j] wave 1 (j = 1, 2, 5, 6), wave 2 (every j), wave 1     the multiple (j + 1) P in tab[j] and
+    //              wave 3 (j = 3, 4, 7)     (j = 7 .. 2), wave 3 (j = 1) tabphx[j], until entry j replaces it
     //   spost[5+p] wave 2 p + 1             wave 2 p, in phase D         xg[p] (pair p's chain-1 point)
     //   hpost[j]   the j-th summing helper  the j + 1-th                 pt[j] (the comb partials so far)
-    // The last summing helper leaves the G part in pt[3]; it and wave 1..3's other reads of helper results
-    // lie behind phase D's first barrier, which the helpers join after their last store.  The rule: no wave
+    // The last summing helper leaves the G part in pt[3]; that and every other read of a helper's results (the
+    // root helper's sq, rflag, yok among them: K = Zc^2 w comes with the table) lie behind phase D's first
+    // barrier, which the helpers join after their last store.  The rule: no wave
     // waits for a flag whose poster can be parked at a barrier that needs the waiter.  Every poster above
     // posts before its first barrier after the start, and waits before that only for flags higher in this
-    // table (wave 0 and helper 3 for none; wave 1 for none).
-    // The chain points cannot reuse the table's LDS: xg holds them ([pair] chain point / sum S / X3 Y3).
-    uint32_t spost[8];
+    // table (wave 0 and helper 3 for none).  The table's flags (spost[1], [3], [4], [7] .. [15]) are
+    // trio_table_shared's (ec26_trio.h, which orders them and shows that no wait of them has a cycle); the three
+    // table waves wait for nothing else before they post.
+    // The chain points cannot reuse the table's LDS: xg holds them ([pair] chain point / sum S / X3 Y3); before
+    // phase D it is the table build's (the prefix products), as tsuf (the suffix products).  kw is K = Zc^2 w,
+    // canonical limbs, from wave 2 to phase D.
+    uint32_t spost[kTfSlots];
     uint32_t hpost[4];
     uint32_t xg[2][kTrioWords][64];
+    uint32_t tsuf[6][10][64];
+    uint32_t kw[10][64];
+};
+// lds_flag_wait for four flags at once: the four loads of a round go out together, the acquire fence follows
+// the round that read all of them set
+__device__ __forceinline__ void lds_flag_wait4(uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* d) {
+    for (;;) {
+        const uint32_t x = __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t y = __hip_atomic_load(b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t z = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t u = __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (x != 0u && y != 0u && z != 0u && u != 0u) break;
+        __builtin_amdgcn_s_sleep(1);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// trio_table_shared's hand-off on the device: the flags of Trio26RecoverLds::spost
+struct TrioTableFlags {
+    uint32_t* f;
+    __device__ __forceinline__ void post(int s) { lds_flag_post(f + s); }
+    __device__ __forceinline__ void wait(int s) { lds_flag_wait(f + s); }
+    __device__ __forceinline__ void stamp(int k) {
+        COOP_T(k);
+        (void)k;
+    }
 };
 __device__ __forceinline__ void lds_store_limbs26(uint32_t (*dst)[64], const fe26& a, int lane) {
     fe26 t;
@@ -1161,8 +1198,9 @@ __device__ __forceinline__ void trio_sum_partials(TrioPt& A, const Trio26Lds& L,
 // given), s^-1 instead of r^-1, and the projective x-check instead of the affine inversion and the
 // address hash.  Shared: recover_w (both recoveries), comb_share (all three), trio_glv_chain (both trio
 // kernels); coop26_table_to_lds, the scalar phase (coop26_post_e_inv, coop26_u1_glv) and trio_sum_partials are
-// coop26_body's and trio26_verify_body's (the eight-wave recovery body has trio_table_staged, its own scalar
-// phase on wave 0 and trio_recover_helper); trio_recover_tail names the recovery kernel's last phase.
+// coop26_body's and trio26_verify_body's (the eight-wave recovery body has trio_table_shared on waves 1 .. 3
+// (ec26_trio.h), its own scalar phase on wave 0 and trio_recover_helper); trio_recover_tail names the recovery
+// kernel's last phase.
 
 // Recovery, waves 1 and 2: X = r (+ n when v & 2) as fe26 and w = X^3 + 7 (m 2); returns ok and, for
 // v & 2, r < p - n.  No LDS.
@@ -1526,87 +1564,6 @@ __device__ __forceinline__ void trio_recover_tail(const IO& io, uint32_t* mbuf, 
     }
 }
 
-// coop26_table_to_lds<true> within the register budget of two waves per SIMD: the same multiples
-// (multiples8_26), the same co-Z rescale (coz_table26) and the same stores, value for value, but the eight
-// Jacobian multiples wait in the table's own LDS rows of column `lane` (X, Y raw limbs in L.tab[j], Z in
-// L.tabphx[j]; magnitudes as CurveK1x returns them: 10, 10, 2) instead of 240 registers, and each entry
-// replaces its multiple once that is read back.  A lane touches its own column only.
-__device__ __forceinline__ void trio_table_staged(Trio26RecoverLds& L, const Aff26& P, int lane) {
-    const auto put = [&](int j, const Jac26& J) {
-#pragma unroll
-        for (int q = 0; q < 10; ++q) {
-            L.tab[j][q][lane] = J.X.v[q];
-            L.tab[j][10 + q][lane] = J.Y.v[q];
-            L.tabphx[j][q][lane] = J.Z.v[q];
-        }
-    };
-    const auto get_z = [&](fe26& Z, int j) {
-#pragma unroll
-        for (int q = 0; q < 10; ++q) Z.v[q] = L.tabphx[j][q][lane];
-        F26_SETM(Z, 2);
-    };
-    {
-        Jac26 A, B, N;  // T[j] = (j + 1) P
-        CurveK1x::from_aff(B, P);
-        CurveK1x::dbl(A, B);      // 2 P
-        put(1, A);
-        CurveK1x::madd(B, A, P);  // 3 P
-        put(2, B);
-        CurveK1x::dbl(N, A);      // 4 P
-        put(3, N);
-        CurveK1x::dbl(A, B);      // 6 P
-        put(5, A);
-        CurveK1x::madd(B, A, P);  // 7 P
-        put(6, B);
-        CurveK1x::madd(B, N, P);  // 5 P
-        put(4, B);
-        CurveK1x::dbl(A, N);      // 8 P
-        put(7, A);
-    }
-    // s_j = Zc / Z_j from prefix products and a running suffix, the entries from the top down (coz_table26)
-    fe26 pre[7], suf, Zc, beta, Zj;
-    fe26_one(pre[0]);
-    get_z(pre[1], 1);
-    Unroll<2, 7>::run([&](auto J) {
-        get_z(Zj, J);
-        fe26_mul(pre[J], pre[J - 1], Zj);
-    });
-    get_z(Zj, 7);
-    fe26_mul(Zc, pre[6], Zj);
-    fe26_const(beta, kGlvBeta);
-    Unroll<0, 8>::run([&](auto J) {
-        constexpr int j = 7 - decltype(J)::value;
-        fe26 sj, s2, s3, X, Y, bx;
-        if constexpr (j == 0) {
-            fe26_copy(X, P.x);
-            fe26_copy(Y, P.y);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 10; ++q) {
-                X.v[q] = L.tab[j][q][lane];
-                Y.v[q] = L.tab[j][10 + q][lane];
-            }
-            F26_SETM(X, 10);
-            F26_SETM(Y, 10);
-            get_z(Zj, j);
-        }
-        if constexpr (j == 7) fe26_copy(sj, pre[6]);
-        else if constexpr (j <= 1) fe26_copy(sj, suf);
-        else fe26_mul(sj, pre[j - 1], suf);
-        if constexpr (j == 7) fe26_copy(suf, Zj);
-        else if constexpr (j >= 1) fe26_mul(suf, suf, Zj);
-        fe26_sqr(s2, sj);
-        fe26_mul(s3, s2, sj);
-        fe26_mul(X, X, s2);
-        fe26_mul(Y, Y, s3);
-        fe26_mul(bx, X, beta);
-        lds_store_limbs26(L.tab[j], X, lane);
-        lds_store_limbs26(L.tab[j] + 10, Y, lane);
-        lds_store_limbs26(L.tabphx[j], bx, lane);
-    });
-    lds_store_fe26(L.zc, Zc, lane);
-}
-
 // a helper's wait of the recovery kernel: as lds_flag_wait, with a longer sleep between the loads (the
 // helper shares its SIMD with a chain wave, and nothing it waits for is urgent)
 __device__ __forceinline__ void lds_flag_wait_idle(uint32_t* f) {
@@ -1638,14 +1595,10 @@ __device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const I
         fe26_cmov(y, ny, (y.v[0] & 1u) != (v & 1u));
         if (lane < kTrioTxs) {
 #pragma unroll
-            for (int q = 0; q < 10; ++q) {
-                L.sq[0][q][lane] = w.v[q];
-                L.sq[1][q][lane] = y.v[q];
-            }
+            for (int q = 0; q < 10; ++q) L.sq[q][lane] = y.v[q];
         }
         L.rflag[lane] = okr ? 2u : 0u;
         L.yok[lane] = on ? 1u : 0u;
-        lds_flag_post(&L.spost[2]);
         COOP_T(6);
     } else if (h == 3) {
         fe e;
@@ -1684,9 +1637,9 @@ __device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const I
 }
 
 // tx_verify_trio26_kernel, eight waves.  Waves 0..3 do only what the chains need: wave 0 r^-1 mod n and at
-// once u2 = s / r and its GLV split, wave 1 the table of R' = (w x, w^2); each enters phase C behind the two
-// flags of those.  Waves 4..7 are helpers (trio_recover_helper): the digest, u1, the comb windows of u1 G and
-// their sum, and the whole square root, all of it needed in phase D only.  A helper shares a SIMD with a
+// once u2 = s / r and its GLV split, waves 1 .. 3 the table of R' = (w x, w^2) between them (trio_table_shared,
+// with K = Zc^2 w for phase D); each enters phase C behind the four flags of those.  Waves 4..7 are helpers
+// (trio_recover_helper): the digest, u1, the comb windows of u1 G and their sum, and the whole square root, all of it needed in phase D only.  A helper shares a SIMD with a
 // chain wave and takes the issue slots that a lone wave leaves empty (a gfx950 SIMD is 32 lanes wide: a
 // wave64 VALU op occupies it for 2 cycles and a lone wave issues one per 4).  The helpers join
 // every barrier of phase D and of trio_recover_tail and do nothing between them.
@@ -1705,7 +1658,7 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         L.post[1] = 0u;
         L.post[2] = 0u;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) L.spost[q] = 0u;
+        for (int q = 0; q < kTfSlots; ++q) L.spost[q] = 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) L.hpost[q] = 0u;
     }
@@ -1723,7 +1676,7 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         bool ok = false;
         fe_zero(r);
         fe_zero(s);
-        if (active && (wave <= 1 || wave == 4 + 2)) ok = io.rsv(i, r, s, v);
+        if (active && (wave <= 3 || wave == 4 + 2)) ok = io.rsv(i, r, s, v);
         if (helper) {
             trio_recover_helper(L, io, i, active, ok, r, v, tab, tab_bits, wave - 4, lane);
             COOP_T(1);
@@ -1741,8 +1694,10 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
                 lds_flag_post(&L.post[0]);
                 COOP_T(7);
                 FieldN1::mul(u2, s, rinv);
+                COOP_T(10);
                 bool neg1, neg2;
                 glv_split(k1, neg1, k2, neg2, u2);
+                COOP_T(11);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     L.k[0][q][lane] = k1.v[q];
@@ -1751,19 +1706,23 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
                 L.flags[lane] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
                 lds_flag_post(&L.spost[0]);
                 COOP_T(8);
-            } else if (wave == 1) {
-                fe26 X, rhs;
+            } else {  // the table of R' on waves 1, 2, 3 (trio_table_shared), each from its own r, v
+                fe26 X, rhs, beta;
                 recover_w(X, rhs, r, v, ok);
                 Aff26 R;
                 fe26_mul(R.x, rhs, X);  // w x
                 fe26_sqr(R.y, rhs);     // w^2
-                trio_table_staged(L, R, lane);
-                lds_flag_post(&L.spost[1]);
-                COOP_T(6);
+                fe26_const(beta, kGlvBeta);
+                TrioTableFlags tf{L.spost};
+                if (wave == 1) trio_table_shared<kTableLong>(L, tf, R, rhs, beta, lane);
+                else if (wave == 2) trio_table_shared<kTablePrefix>(L, tf, R, rhs, beta, lane);
+                else trio_table_shared<kTableShort>(L, tf, R, rhs, beta, lane);
             }
             COOP_T(1);
-            lds_flag_wait(&L.spost[0]);
-            lds_flag_wait(&L.spost[1]);
+            // (the scalars' flag and the table's three in one round of loads: a wait apiece cost the chain start
+            // an LDS round trip each after the last flag was up)
+            lds_flag_wait4(&L.spost[0], &L.spost[kTfDone[kTableLong]], &L.spost[kTfDone[kTablePrefix]],
+                           &L.spost[kTfDone[kTableShort]]);
             COOP_T(9);
             // (the chain waves are the older wave of their SIMD and win its arbitration by age; one s_setprio
             // for them here measured 0.3383 against 0.3393 ms with run-to-run spreads of 0.0011 and 0.0025:
@@ -1787,11 +1746,10 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
     const bool tactive = ti < n;
     fe ax, ay;
     bool ok2 = false;
-    const auto load_zc_w = [&](fe26& zc, fe26& w) {
-        lds_load_fe26(zc, L.zc, tl);
+    const auto load_k = [&](fe26& K) {  // K = Zc^2 w, stored with the table (behind wave 2's spost[3])
 #pragma unroll
-        for (int q = 0; q < 10; ++q) w.v[q] = L.sq[0][q][tl];
-        F26_SETM(w, 2);
+        for (int q = 0; q < 10; ++q) K.v[q] = L.kw[q][tl];
+        F26_SETM(K, 1);
     };
     const auto load_g = [&](TrioPt& G) {  // the G part, from the helpers' one-lane sum
         Jac26 J;
@@ -1811,11 +1769,8 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         trio_load(P1, xbuf, lane);
         trio_add(acc, acc, P1, T);
         trio_store(xbuf, acc, lane);
-        fe26 zc, w, K;
-        lds_flag_wait(&L.spost[2]);  // w is the root helper's
-        load_zc_w(zc, w);
-        fe26_sqr(K, zc);
-        fe26_mul(K, K, w);
+        fe26 K;
+        load_k(K);
         trio_scale_xz(SE, acc, K, T);
     }
     __syncthreads();  // every wave is past phase C and every helper past its last store; S and T are in LDS
@@ -1838,13 +1793,12 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         TrioPt S, G;
         trio_load(S, xbuf, lane);
         load_g(G);
-        fe26 y, zc, w, K, l;
-        load_zc_w(zc, w);
-        fe26_sqr(K, zc);
-        fe26_mul(K, K, w);
+        fe26 y, zc, K, l;
+        load_k(K);
+        lds_load_fe26(zc, L.zc, tl);
         trio_scale_xz(SE, S, K, T);
 #pragma unroll
-        for (int q = 0; q < 10; ++q) y.v[q] = L.sq[1][q][tl];
+        for (int q = 0; q < 10; ++q) y.v[q] = L.sq[q][tl];
         F26_SETM(y, 1);
         COOP_T(4);
         fe26_mul(l, zc, y);
