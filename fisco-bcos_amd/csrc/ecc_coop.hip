@@ -1781,9 +1781,11 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         fe26 Z3;
         trio_add_z(Z3, G, SE, T);
         COOP_T(4);
+        // Z^-1 on the trio (modinv30.h): Z3 is lane 2's, the inversion takes it to role 0 and hands Z^-1 back to
+        // lane 2 (on one wave: its partner is busy with the last addition, and the helpers are parked)
         fe z, zi;
         fe26_to_fe(z, Z3);
-        FieldInv<FieldK1>::inv_pipe(zi, z);  // (on one wave: its partner is busy with the last addition)
+        FieldInv<FieldK1>::inv_trio<2, 2>(zi, z, T, lane);
         COOP_T(5);
         fe26 zi26;
         fe26_from_fe(zi26, zi);

@@ -7,17 +7,9 @@
 // (further batches are then exact no-ops).  Values are plain residues in [0, m).
 #pragma once
 #include "fe.h"
+#include "modinv30.h"
 
 namespace bcosgpu {
-
-struct S30 {
-    int32_t v[9];
-};
-
-struct ModInfo30 {
-    int32_t m[9];    // modulus in signed-30 form
-    uint32_t inv30;  // m^-1 mod 2^30
-};
 
 __device__ __constant__ static const ModInfo30 kMod30K1P = {
     {1073740847, 1073741819, 1073741823, 1073741823, 1073741823, 1073741823, 1073741823, 1073741823, 65535}, 769313487u};
@@ -27,8 +19,6 @@ __device__ __constant__ static const ModInfo30 kMod30P2 = {
     {1073741823, 1073741823, 15, 1073741760, 1073741823, 1073741823, 1073741823, 1073725439, 65535}, 1073741823u};
 __device__ __constant__ static const ModInfo30 kMod30N2 = {
     {970277155, 250597412, 476074677, 16243400, 1073741682, 1073741823, 1073741823, 1073725439, 65535}, 231405195u};
-
-static constexpr int32_t kM30 = 0x3fffffff;
 
 __device__ __forceinline__ void fe_to_s30(S30& r, const fe& a) {
 #pragma unroll
@@ -50,34 +40,6 @@ __device__ __forceinline__ void s30_to_fe(fe& r, const S30& a) {
         if (sh > 28 && i + 2 < 9) x |= static_cast<uint32_t>(a.v[i + 2]) << (60 - sh);
         r.v[w] = x;
     }
-}
-
-// 30 divsteps on the low bits of f, g; transition matrix (u, v, q, r) scaled by 2^30:
-// u f0 + v g0 = f 2^30, q f0 + r g0 = g 2^30.  zeta = -(delta + 1/2).
-__device__ __forceinline__ int32_t divsteps_30(int32_t zeta, uint32_t f, uint32_t g, int32_t t[4]) {
-    uint32_t u = 1, v = 0, q = 0, r = 1;
-#pragma unroll
-    for (int i = 0; i < 30; ++i) {
-        uint32_t c1 = static_cast<uint32_t>(zeta >> 31);  // zeta < 0
-        const uint32_t c2 = 0u - (g & 1u);                 // g odd
-        const uint32_t x = (f ^ c1) - c1, y = (u ^ c1) - c1, z = (v ^ c1) - c1;
-        g += x & c2;
-        q += y & c2;
-        r += z & c2;
-        c1 &= c2;
-        zeta = (zeta ^ static_cast<int32_t>(c1)) - 1;
-        f += g & c1;
-        u += q & c1;
-        v += r & c1;
-        g >>= 1;
-        u <<= 1;
-        v <<= 1;
-    }
-    t[0] = static_cast<int32_t>(u);
-    t[1] = static_cast<int32_t>(v);
-    t[2] = static_cast<int32_t>(q);
-    t[3] = static_cast<int32_t>(r);
-    return zeta;
 }
 
 // 30 divsteps as divsteps_30, in variable time (the var-time loop of libsecp256k1's modinv32, restated):
@@ -146,79 +108,6 @@ __device__ __forceinline__ int32_t divsteps_30_var(int32_t eta, uint32_t f, uint
     return eta;
 }
 
-// (f, g) <- t (f, g) / 2^30 (exact)
-__device__ __forceinline__ void update_fg_30(S30& f, S30& g, const int32_t t[4]) {
-    const int64_t u = t[0], v = t[1], q = t[2], r = t[3];
-    int64_t cf = u * f.v[0] + v * g.v[0];
-    int64_t cg = q * f.v[0] + r * g.v[0];
-    cf >>= 30;
-    cg >>= 30;
-#pragma unroll
-    for (int i = 1; i < 9; ++i) {
-        cf += u * f.v[i] + v * g.v[i];
-        cg += q * f.v[i] + r * g.v[i];
-        f.v[i - 1] = static_cast<int32_t>(cf) & kM30;
-        cf >>= 30;
-        g.v[i - 1] = static_cast<int32_t>(cg) & kM30;
-        cg >>= 30;
-    }
-    f.v[8] = static_cast<int32_t>(cf);
-    g.v[8] = static_cast<int32_t>(cg);
-}
-
-// (d, e) <- (t (d, e) + m (md, me)) / 2^30, md/me chosen so the division is exact; keeps d, e in
-// (-2m, m).
-__device__ __forceinline__ void update_de_30(S30& d, S30& e, const int32_t t[4], const ModInfo30& mi) {
-    const int32_t u = t[0], v = t[1], q = t[2], r = t[3];
-    const int32_t sd = d.v[8] >> 31, se = e.v[8] >> 31;
-    int32_t md = (u & sd) + (v & se);
-    int32_t me = (q & sd) + (r & se);
-    int64_t cd = static_cast<int64_t>(u) * d.v[0] + static_cast<int64_t>(v) * e.v[0];
-    int64_t ce = static_cast<int64_t>(q) * d.v[0] + static_cast<int64_t>(r) * e.v[0];
-    md -= static_cast<int32_t>((mi.inv30 * static_cast<uint32_t>(cd) + static_cast<uint32_t>(md)) & kM30);
-    me -= static_cast<int32_t>((mi.inv30 * static_cast<uint32_t>(ce) + static_cast<uint32_t>(me)) & kM30);
-    cd += static_cast<int64_t>(mi.m[0]) * md;
-    ce += static_cast<int64_t>(mi.m[0]) * me;
-    cd >>= 30;
-    ce >>= 30;
-#pragma unroll
-    for (int i = 1; i < 9; ++i) {
-        cd += static_cast<int64_t>(u) * d.v[i] + static_cast<int64_t>(v) * e.v[i];
-        ce += static_cast<int64_t>(q) * d.v[i] + static_cast<int64_t>(r) * e.v[i];
-        cd += static_cast<int64_t>(mi.m[i]) * md;
-        ce += static_cast<int64_t>(mi.m[i]) * me;
-        d.v[i - 1] = static_cast<int32_t>(cd) & kM30;
-        cd >>= 30;
-        e.v[i - 1] = static_cast<int32_t>(ce) & kM30;
-        ce >>= 30;
-    }
-    d.v[8] = static_cast<int32_t>(cd);
-    e.v[8] = static_cast<int32_t>(ce);
-}
-
-// r in (-2m, m) -> sign * r mod m in [0, m)
-__device__ __forceinline__ void normalize_30(S30& r, int32_t sign, const ModInfo30& mi) {
-    int32_t ca = r.v[8] >> 31;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.v[i] += mi.m[i] & ca;
-    const int32_t cn = sign >> 31;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.v[i] = (r.v[i] ^ cn) - cn;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        r.v[i + 1] += r.v[i] >> 30;
-        r.v[i] &= kM30;
-    }
-    ca = r.v[8] >> 31;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.v[i] += mi.m[i] & ca;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        r.v[i + 1] += r.v[i] >> 30;
-        r.v[i] &= kM30;
-    }
-}
-
 // r = x^-1 mod m (x in [0, m); x = 0 gives 0)
 __device__ __forceinline__ void modinv_safegcd(fe& r, const fe& x, const ModInfo30& mi) {
     S30 d, e, f, g;
@@ -278,6 +167,22 @@ __device__ __forceinline__ void modinv_safegcd_pipe(fe& r, const fe& x, const Mo
     }
     update_de_30(d, e, t, mi);
     normalize_30(d, f.v[8], mi);
+    s30_to_fe(r, d);
+}
+
+// r = x^-1 mod m on a lane trio (modinv30.h, modinv_safegcd_trio): x in [0, m) on the lanes of role SRC, r on
+// the lanes of role DST.  x travels to role 0, which holds (f, g), in one DPP round of eight words; the
+// phantom lane's fetch leaves the row and reads 0, whose inverse is 0.
+template <int SRC, int DST>
+__device__ __forceinline__ void modinv_trio(fe& r, const fe& x, const ModInfo30& mi, const TrioLane& T, int lane) {
+    static_assert(SRC >= 0 && SRC <= 2, "a trio has roles 0, 1, 2");
+    fe x0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        x0.v[i] = SRC == 0 ? x.v[i] : SRC == 1 ? trio::dpp<trio::kR1>(x.v[i]) : trio::dpp<trio::kR2>(x.v[i]);
+    S30 g, d;
+    fe_to_s30(g, x0);
+    modinv_safegcd_trio<DST>(d, g, mi, T, lane);
     s30_to_fe(r, d);
 }
 
@@ -427,6 +332,15 @@ struct FieldInv<FieldK1> {
         fe_copy(t, a);
         FieldK1::normalize(t);
         modinv_safegcd_var(r, t, kMod30K1P);
+    }
+    // a on the lanes of role SRC of every lane trio (ec26_trio.h), a^-1 on the lanes of role DST: the three
+    // lanes of a trio share one inversion (modinv_safegcd_trio)
+    template <int SRC, int DST>
+    __device__ static __forceinline__ void inv_trio(fe& r, const fe& a, const TrioLane& T, int lane) {
+        fe t;
+        fe_copy(t, a);
+        FieldK1::normalize(t);
+        modinv_trio<SRC, DST>(r, t, kMod30K1P, T, lane);
     }
 };
 // PIPE: 0 plain, 1 pipelined, 2 variable time

@@ -1,7 +1,8 @@
 // invbench.hip -- cycles of the safegcd inversion (modinv.h) on a lone wave: the plain loop against the
 // software-pipelined one (the (d, e) update beside the next batch's divsteps), plus the parts of one
 // batch (30 divsteps, the (f, g) and (d, e) updates), and agreement of the two variants on random
-// inputs mod p (secp256k1) and mod n.
+// inputs mod p (secp256k1) and mod n.  And the inversion on lane trios (modinv30.h, modinv_safegcd_trio): one
+// value per trio, 20 to the wave, each result against modinv_safegcd's, and its cycles on the same lone wave.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
@@ -28,6 +29,27 @@ __global__ void inv_kernel(const fe* in, fe* out_a, fe* out_b, int which_mod, ui
         cyc[0] = t1 - t0;
         cyc[1] = t3 - t2;
     }
+}
+
+// the trio inversion: trio t of the wave (lane positions 3j .. 3j + 2 of each 16-lane row) inverts in[t]; the
+// value arrives on role 0 and the result is taken on role 2, as the recovery kernel's phase D has it
+__global__ void trio_kernel(const fe* in, fe* out_a, fe* out_b, int which_mod, uint64_t* cyc) {
+    const ModInfo30& mi = which_mod ? kMod30N1 : kMod30K1P;
+    const int lane = threadIdx.x, pos = lane & 15;
+    const TrioLane T(lane);
+    const int t = (lane >> 4) * 5 + (pos < 15 ? pos / 3 : 4);
+    const fe x = in[t];
+    fe a, b;
+    modinv_safegcd(a, x, mi);
+    __syncthreads();
+    uint64_t t0 = clock64();
+    modinv_trio<0, 2>(b, x, mi, T, lane);
+    uint64_t t1 = clock64();
+    if (T.r2) {
+        out_a[t] = a;
+        out_b[t] = b;
+    }
+    if (threadIdx.x == 0) cyc[0] = t1 - t0;
 }
 
 __global__ void parts_kernel(const fe* in, uint64_t* cyc, int32_t* sink) {
@@ -139,6 +161,32 @@ int main() {
             printf("%s[%llu, %llu, %llu, %llu]", (m | uu) ? ", " : "", (unsigned long long)cv[m][uu][0],
                    (unsigned long long)cv[m][uu][1], (unsigned long long)cv[m][uu][2], (unsigned long long)cv[m][uu][3]);
     printf("]}\n");
+    // the trio inversion, both moduli: 20 values (among them 0 and 1) per wave
+    int trio_bad = 0;
+    uint64_t ct[2] = {0, 0};
+    {
+        std::vector<fe> xt(x.begin(), x.begin() + 20);
+        for (int i = 0; i < 8; ++i) {
+            xt[7].v[i] = 0;
+            xt[13].v[i] = i == 0;
+        }
+        (void)hipMemcpy(dx, xt.data(), 20 * sizeof(fe), hipMemcpyHostToDevice);
+        for (int m = 0; m < 2; ++m) {
+            for (int rep = 0; rep < 2; ++rep) {
+                hipLaunchKernelGGL(trio_kernel, dim3(1), dim3(64), 0, 0, dx, da, db, m, dc);
+                (void)hipMemcpy(&ct[m], dc, 8, hipMemcpyDeviceToHost);
+            }
+            std::vector<fe> a(20), b(20);
+            (void)hipMemcpy(a.data(), da, 20 * sizeof(fe), hipMemcpyDeviceToHost);
+            (void)hipMemcpy(b.data(), db, 20 * sizeof(fe), hipMemcpyDeviceToHost);
+            for (int i = 0; i < 20; ++i)
+                for (int k = 0; k < 8; ++k) trio_bad += a[i].v[k] != b[i].v[k];
+        }
+        (void)hipMemcpy(dx, x.data(), 64 * sizeof(fe), hipMemcpyHostToDevice);
+    }
+    printf("{\"trio_mismatched_words\": %d, \"inv_p_trio_cycles\": %llu, \"inv_n_trio_cycles\": %llu}\n", trio_bad,
+           (unsigned long long)ct[0], (unsigned long long)ct[1]);
+    bad += trio_bad;
     uint64_t p[3];
     hipLaunchKernelGGL(parts_kernel, dim3(1), dim3(64), 0, 0, dx, dc, dk);
     (void)hipMemcpy(p, dc, 24, hipMemcpyDeviceToHost);
