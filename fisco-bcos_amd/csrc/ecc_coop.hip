@@ -1132,6 +1132,18 @@ __device__ __forceinline__ void trio_entry(Aff26& S, const Trio26Lds& L, int tl,
     fe26_cmov(S.y, ny, (d < 0) != neg);
 }
 
+// The pad in front of trio_glv_chain's window loop (see there), and the offset of the loop's head within its
+// 64-byte line that results (one preheader instruction comes on top of the pad: 4 pad + 4), in both trio kernels.
+// Measured over the sixteen offsets (profiles/trio_loop_pin.json, tools/coopbench.hip): what counts is the head
+// modulo 8 -- at 4, 12, .. 60 phase C takes 529-534k cycles and the kernel ends at 719-722k, at 0, 8, .. 56
+// 538-546k and 728-733k (unpinned, the loop had come to lie at 8).  As libraries, alternated with the unpinned
+// one on C2 (profiles/trio_scalars_ab.json): 0.31005 ms per step at 12, 0.31075 at 28, 0.31467 unpinned; 12
+// ships.  The known-key kernel at 10,240 signatures does not move (0.3280-0.3288 ms at 12, 0.3282-0.3287
+// unpinned at 52, both 4 modulo 8), so one pad serves both callers.
+static constexpr int kTrioLoopPad = 2;
+static constexpr int kTrioLoopHeadMod64 = 12;
+static_assert(kTrioLoopHeadMod64 == (4 * kTrioLoopPad + 4) % 64, "the pad, then one preheader instruction");
+
 // Phase C of both trio kernels, one GLV chain on a trio: acc = +-k R (chain 0) or +-k phi(R) (chain 1) for
 // the half scalar k = L.k[chain] of tx tl and its sign in tflags (bit 2 / bit 3), on the table's curve.
 // Digits 32 and 31 go together (trio_chain_start), then 31 lean windows (trio_window on a TrioAcc: four
@@ -1144,6 +1156,13 @@ __device__ __forceinline__ void trio_entry(Aff26& S, const Trio26Lds& L, int tl,
 // which the addition handles.  The chain's start adds b <= 1 to K = 2a, a <= 8: 2a = +-b only for a = 0, the
 // flag again.  (Reading the table entry before the window's doublings, to take the LDS latency off the
 // first level, measured no gain: 893k cycles either way.)
+//
+// The window loop is 28 KB of straight code, a little under half the 64 KB instruction cache that a CU's pair
+// shares, and its time depends on where its head falls within a 64-byte line: every edit to code in front of it
+// used to move it, by up to 2 % of the kernel.  So the loop is pinned: an alignment to a line, then kTrioLoopPad
+// s_nop.  The compiler may put preheader instructions between the pad and the head;
+// tests/test_trio_loop_pin.py reads the head's offset from the built code and compares it with
+// kTrioLoopHeadMod64.
 __device__ __forceinline__ void trio_glv_chain(TrioPt& acc, const Trio26Lds& L, int chain, int tl, uint32_t tflags,
                                                const TrioLane& T) {
     fe k;
@@ -1157,6 +1176,7 @@ __device__ __forceinline__ void trio_glv_chain(TrioPt& acc, const Trio26Lds& L, 
     shl4_128(k);  // booth_digit128 goes on at digit 30
     TrioAcc la;
     trio_acc_from(la, acc);
+    asm volatile(".p2align 6\n\t.rept %0\n\ts_nop 0\n\t.endr" ::"n"(kTrioLoopPad));
 #pragma unroll 1
     for (int w = 30; w >= 0; --w)
         trio_window(la, booth_digit128(k), [&](Aff26& S, int d) { trio_entry(S, L, tl, d, neg, phi); }, T);

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "ec.h"
 #include "engine.h"
+#include "glv_split.h"
 #include "hash_device.h"
 
 namespace bcosgpu {
@@ -36,18 +37,8 @@ __device__ __constant__ static const uint32_t kK1PminusN[8] = {0x2fc9baeeu, 0x40
                                                             0x00000001u, 0x00000000u, 0x00000000u, 0x00000000u};
 __device__ __constant__ static const uint32_t kN1Half[8] = {0x681b20a0u, 0xdfe92f46u, 0x57a4501du, 0x5d576e73u,
                                                          0xffffffffu, 0xffffffffu, 0xffffffffu, 0x7fffffffu};
-// GLV endomorphism of secp256k1: lambda*(x, y) = (beta*x, y); split constants of libsecp256k1's
-// secp256k1_scalar_split_lambda (|k1|, |k2| < 2^128).  LAMBDA and MINUS_B2 in Montgomery form mod n.
-__device__ __constant__ static const uint32_t kGlvG1[8] = {0x45dbb031u, 0xe893209au, 0x71e8ca7fu, 0x3daa8a14u,
-                                                        0x9284eb15u, 0xe86c90e4u, 0xa7d46bcdu, 0x3086d221u};
-__device__ __constant__ static const uint32_t kGlvG2[8] = {0x8ac47f71u, 0x1571b4aeu, 0x9df506c6u, 0x221208acu,
-                                                        0x0abfe4c4u, 0x6f547fa9u, 0x010e8828u, 0xe4437ed6u};
-__device__ __constant__ static const uint32_t kGlvMB1[8] = {0x0abfe4c3u, 0x6f547fa9u, 0x010e8828u, 0xe4437ed6u,
-                                                         0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u};
-__device__ __constant__ static const uint32_t kGlvMB2M[8] = {0x6a144696u, 0x0cac5e50u, 0xf3ba5939u, 0x1e8a8dc5u,
-                                                          0xba244fceu, 0x176cdf65u, 0x8e173580u, 0xc25575ebu};
-__device__ __constant__ static const uint32_t kGlvLambdaM[8] = {0xc9926c9eu, 0xf07deb3du, 0x83c6944cu, 0x2c93e7adu,
-                                                             0x52697d91u, 0x73a96606u, 0x8558d639u, 0x53284017u};
+// GLV endomorphism of secp256k1: lambda*(x, y) = (beta*x, y).  The split's constants (kGlvG1, kGlvG2, kGlvMB1,
+// kGlvA1, kGlvA2: __constant__ tables too) stand beside its core in glv_split.h.
 __device__ __constant__ static const uint32_t kGlvBeta[8] = {0x719501eeu, 0xc1396c28u, 0x12f58995u, 0x9cf04975u,
                                                           0xac3434e9u, 0x6e64479eu, 0x657c0710u, 0x7ae96a2bu};
 // SM2 (Montgomery form mod p)
@@ -249,43 +240,15 @@ __device__ __forceinline__ void booth_mul(Jac& acc, const fe& k_plain, const Aff
 }
 
 // k = k1 + k2*lambda (mod n) with |k1|, |k2| < 2^128 (libsecp256k1 split_lambda); returns the
-// magnitudes and signs.
+// magnitudes (upper limbs zero) and signs, for k < n.  The halves are exact small integers (glv_split.h:
+// two rounding products, four truncated ones, no arithmetic mod n).
 __device__ __forceinline__ void glv_split(fe& k1, bool& neg1, fe& k2, bool& neg2, const fe& k) {
-    uint32_t t[16];
-    fe g, c1, c2, x, y;
-    fe_set(g, kGlvG1);
-    mul_512(t, k, g);
-    uint32_t c = 0;
+    uint32_t n1, n2;
+    glv_split_core(k1.v, n1, k2.v, n2, k.v);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) c1.v[i] = addc32(t[12 + i], i == 0 ? (t[11] >> 31) : 0u, c, c);
-#pragma unroll
-    for (int i = 4; i < 8; ++i) c1.v[i] = 0;
-    fe_set(g, kGlvG2);
-    mul_512(t, k, g);
-    c = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c2.v[i] = addc32(t[12 + i], i == 0 ? (t[11] >> 31) : 0u, c, c);
-#pragma unroll
-    for (int i = 4; i < 8; ++i) c2.v[i] = 0;
-    fe_set(g, kGlvMB1);
-    mul_512(t, c1, g);  // < 2^256
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x.v[i] = t[i];
-    reduce_once(x, ParamN1::M);
-    fe_set(g, kGlvMB2M);
-    FieldN1::mul(y, c2, g);  // c2 * (-b2) mod n
-    FieldN1::add(k2, x, y);
-    fe_set(g, kGlvLambdaM);
-    FieldN1::mul(x, k2, g);  // k2 * lambda mod n
-    FieldN1::sub(k1, k, x);
-    fe half, nk;
-    fe_set(half, kN1Half);
-    neg1 = fe_lt(half, k1);
-    FieldN1::neg(nk, k1);
-    fe_cmov(k1, nk, neg1);
-    neg2 = fe_lt(half, k2);
-    FieldN1::neg(nk, k2);
-    fe_cmov(k2, nk, neg2);
+    for (int i = 4; i < 8; ++i) k1.v[i] = k2.v[i] = 0;
+    neg1 = n1 != 0u;
+    neg2 = n2 != 0u;
 }
 
 // acc += (sign * d) * (phi ? lambda : 1) * P over an affine table T[j] = (j+1) P (mixed add)

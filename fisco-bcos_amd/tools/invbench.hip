@@ -52,6 +52,22 @@ __global__ void trio_kernel(const fe* in, fe* out_a, fe* out_b, int which_mod, u
     if (threadIdx.x == 0) cyc[0] = t1 - t0;
 }
 
+// FieldInv<FieldN1>::inv_trio (Montgomery form in and out, from role 2 to role 2), which no kernel calls yet,
+// against FieldInv<FieldN1>::inv_pipe, which the recovery kernel's phase A runs on one lane per value
+__global__ void trio_field_kernel(const fe* in, fe* out_a, fe* out_b) {
+    const int lane = threadIdx.x, pos = lane & 15;
+    const TrioLane T(lane);
+    const int t = (lane >> 4) * 5 + (pos < 15 ? pos / 3 : 4);
+    const fe x = in[t];
+    fe a, b;
+    FieldInv<FieldN1>::inv_pipe(a, x);
+    FieldInv<FieldN1>::inv_trio<2, 2>(b, x, T, lane);
+    if (T.r2) {
+        out_a[t] = a;
+        out_b[t] = b;
+    }
+}
+
 __global__ void parts_kernel(const fe* in, uint64_t* cyc, int32_t* sink) {
     S30 d, e, f, g;
     fe_to_s30(f, in[threadIdx.x]);
@@ -182,6 +198,16 @@ int main() {
             for (int i = 0; i < 20; ++i)
                 for (int k = 0; k < 8; ++k) trio_bad += a[i].v[k] != b[i].v[k];
         }
+        // the Montgomery-form wrapper mod n on the same 20 values
+        hipLaunchKernelGGL(trio_field_kernel, dim3(1), dim3(64), 0, 0, dx, da, db);
+        std::vector<fe> a(20), b(20);
+        (void)hipMemcpy(a.data(), da, 20 * sizeof(fe), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(b.data(), db, 20 * sizeof(fe), hipMemcpyDeviceToHost);
+        int field_bad = 0;
+        for (int i = 0; i < 20; ++i)
+            for (int k = 0; k < 8; ++k) field_bad += a[i].v[k] != b[i].v[k];
+        printf("{\"inv_trio_n1_mismatched_words\": %d}\n", field_bad);
+        trio_bad += field_bad;
         (void)hipMemcpy(dx, x.data(), 64 * sizeof(fe), hipMemcpyHostToDevice);
     }
     printf("{\"trio_mismatched_words\": %d, \"inv_p_trio_cycles\": %llu, \"inv_n_trio_cycles\": %llu}\n", trio_bad,
