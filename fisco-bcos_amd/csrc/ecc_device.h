@@ -901,6 +901,13 @@ struct KeyIO {
 // ------------------------------------------------------------------ SM2 (one lane)
 // e = SM3(Z_A || hash) as 8 big-endian words; X, Y: public key as big-endian word arrays
 __device__ __forceinline__ void sm2_e(uint32_t e[8], const uint32_t X[8], const uint32_t Y[8], const fe& hash_be) {
+#ifdef BCOSGPU_SM2_RAW_E
+    // test seam (lib/libbcosgpu_rawe.so, tests/test_gpu_sm2_raw_e.py): e is the 32 digest bytes themselves,
+    // not reduced, so that a test chooses it; every caller keeps its own reduce_once and x-check
+#pragma unroll
+    for (int i = 0; i < 8; ++i) e[i] = hash_be.v[7 - i];
+    return;
+#endif
     uint32_t V[8], W[16];
 #pragma unroll
     for (int i = 0; i < 8; ++i) V[i] = kZaMid[i];

@@ -151,6 +151,13 @@ def sm2_recover(h, sig):
     return pub.raw if lib().oracle_sm2_recover(_b(h), _b(sig), len(sig), pub) == 0 else None
 
 
+def sm2_za(pub):
+    """Z_A of a 64-byte public key (the default user id): e = SM3(Z_A || digest)."""
+    za = ctypes.create_string_buffer(32)
+    lib().oracle_sm2_za(_b(pub), za)
+    return za.raw
+
+
 def sm2_pubkey(sk):
     pub = ctypes.create_string_buffer(64)
     return pub.raw if lib().oracle_sm2_pubkey(_b(sk), pub) == 0 else None

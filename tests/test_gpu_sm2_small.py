@@ -12,6 +12,10 @@ bcosgpu_set_tx_kernel_policy, against the oracle's verdicts:
 
   tx_verify_sm2_pair_kernel (8 x 32-bit, TxIO only), policy (1, 1, 1, 0): Transaction::verify at 1, 64, 65.
 
+  the trio, pair26 and row (policy (1, 1, 3, 1)) kernels on valid signatures under the keys d G, d in {1, 2, 3, 8,
+  n - 2, n - 3}: the key is then among G's own multiples, so the table of P's multiples meets the comb's entries
+  and, with 4-bit windows and P = G, the joint sums' first additions coincide about once in 16 signatures.
+
 The inputs are signed by the oracle (a zero and an all-ones digest among them), so every case's accepted and
 rejected counts follow from the CPU alone; each case asserts that it saw both and that every unedited item is
 accepted.  A size below 16 runs a pool of 16 items in launches of that size, so that a one-signature launch
@@ -32,6 +36,7 @@ pytestmark = pytest.mark.gpu
 TRIO = (1, 1, 2, 1)
 PAIR26 = (1, 1, 1, 1)
 PAIR32 = (1, 1, 1, 0)
+ROW = (1, 1, 3, 1)
 TRIO_SIZES = [1, 19, 20, 21, 39, 40, 41, 81]
 PAIR_SIZES = [1, 63, 64, 65, 129]
 
@@ -197,3 +202,33 @@ def test_pair26_sm2_known_key_verify_65(gpu, oracle, policy):
 @pytest.mark.parametrize("n", [1, 64, 65])
 def test_pair32_sm2_tx_verify_edges(gpu, oracle, policy, n):
     _tx_case(gpu, oracle, "pair32-tx-%d" % n, n)
+
+
+# ------------------------------------------------------------------ keys among G's small multiples
+_SMALL_KEYS = {}
+
+
+def _small_key_signed(oracle):
+    """32 oracle signatures under each of d = 1, 2, 3, 8, n - 2, n - 3, all valid; built once."""
+    if not _SMALL_KEYS:
+        rng = _rng("small-keys")
+        ds = [1, 2, 3, 8, N_SM2 - 2, N_SM2 - 3]
+        h = rng.integers(0, 256, size=(32 * len(ds), 32), dtype=np.uint8)
+        sig = np.array([np.frombuffer(oracle.sm2_sign(ds[i // 32].to_bytes(32, "big"), h[i].tobytes(), _scalar(rng)),
+                                      dtype=np.uint8) for i in range(len(h))])
+        assert oracle.sm2_verify_batch(h, sig, nthreads=8).all()
+        for k, d in enumerate(ds):
+            assert (sig[32 * k:32 * k + 32, 64:] == np.frombuffer(oracle.sm2_pubkey(d.to_bytes(32, "big")),
+                                                                  dtype=np.uint8)).all()
+        _SMALL_KEYS["v"] = (h, sig, [oracle.sm3(x[64:].tobytes())[12:] for x in sig])
+    return _SMALL_KEYS["v"]
+
+
+@pytest.mark.parametrize("policy", [TRIO, PAIR26, ROW], indirect=True, ids=["trio", "pair26", "row"])
+def test_sm2_recover_keys_among_small_multiples_of_g(gpu, oracle, policy):
+    h, sig, addr = _small_key_signed(oracle)
+    k0 = gpu.key_cache_info(1)["keyed"]
+    _, got_addr, got = gpu.SM2Crypto().recover_batch(h, sig, want_address=True)
+    assert gpu.key_cache_info(1)["keyed"] == k0  # not the registered-key kernel
+    assert got.all(), np.nonzero(~got)[0].tolist()
+    assert [a.tobytes() for a in got_addr] == addr
