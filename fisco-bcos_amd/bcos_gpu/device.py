@@ -165,6 +165,16 @@ def merkle_roots_batch(hasher, width, leaves, block_off, work, roots, stream=Non
                                                _p(work), _p(roots), _s(stream)))
 
 
+def verify(suite, pubs, hashes, sigs, ok, stream=None):
+    """SignatureCrypto::verify with the keys given (bcosgpu_verify_batch_dev): pubs uint8[n,64], hashes
+    uint8[n,32], sigs uint8[n, stride >= 64] (r || s read) -> ok uint8[n].  The generic kernels: no key lookup."""
+    _dev(ok)
+    n = pubs.shape[0]
+    assert hashes.shape[0] == n and sigs.shape[0] == n and ok.numel() == n
+    check(lib().bcosgpu_verify_batch_dev(suite, _p(pubs), _p(hashes), _p(sigs), sigs.shape[1] if n else 64, n, _p(ok),
+                                         _s(stream)))
+
+
 def verify_keyed(suite, slots, hashes, sigs, ok, stream=None):
     """SignatureCrypto::verify against registered keys (bcosgpu_verify_keyed_batch_dev): slots int32[n]
     (from _lib.register_keys), hashes uint8[n,32], sigs uint8[n, stride >= 64] (r || s read) -> ok uint8[n]."""

@@ -1148,20 +1148,22 @@ __device__ __forceinline__ bool secp256k1_verify_lane26(const fe& hash_be, const
     Jac26 QG, QP, Q;
     glv_mul_k1_26<false>(QP, u2, P, nullptr);
     comb_mul26_rt(QG, u1, tab);
-    CurveK1x::add(Q, QG, QP);  // X m 6
+    // X m 6 from the addition proper, m 10 where it doubles (QG == QP) and the operand's own, up to m 10,
+    // where the other is infinity (u1 = 0)
+    CurveK1x::add(Q, QG, QP);
     ok = ok && !Q.inf;
     fe26 z2, rhs, R, d;
     fe26_sqr(z2, Q.Z);
     fe26_from_fe(R, r);
     fe26_mul(rhs, R, z2);
-    fe26_sub<7>(d, rhs, Q.X);
+    fe26_sub<11>(d, rhs, Q.X);
     bool match = fe26_is_zero(d);
     fe r2;
     const uint32_t carry = fe_add_k(r2, r, ParamN1::M);
     if (carry == 0u && fe_lt_k(r2, FieldK1::P)) {
         fe26_from_fe(R, r2);
         fe26_mul(rhs, R, z2);
-        fe26_sub<7>(d, rhs, Q.X);
+        fe26_sub<11>(d, rhs, Q.X);
         match = match || fe26_is_zero(d);
     }
     return ok && match;

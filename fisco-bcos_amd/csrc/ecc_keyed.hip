@@ -115,8 +115,8 @@ struct KeyedSuite<BCOSGPU_SUITE_SECP256K1> {
     __device__ static __forceinline__ void sqr(F& r, const F& a) { fe26_sqr(r, a); }
     __device__ static __forceinline__ void mul(F& r, const F& a, const F& b) { fe26_mul(r, a, b); }
     __device__ static __forceinline__ bool is_zero(const F& a) { return fe26_is_zero(a); }
-    // rhs - X of the x-check.  acc.X <= 9: an addition may pass a mixed sum through
-    __device__ static __forceinline__ void sub_x(F& d, const F& rhs, const F& X) { fe26_sub<10>(d, rhs, X); }
+    // rhs - X of the x-check.  acc.X <= 10: an addition may pass a mixed sum through (9) or double (10)
+    __device__ static __forceinline__ void sub_x(F& d, const F& rhs, const F& X) { fe26_sub<11>(d, rhs, X); }
     __device__ static __forceinline__ bool on_curve(const Aff& P) {  // y^2 = x^3 + 7
         fe26 l, rr, t, seven;
         fe26_sqr(l, P.y);

@@ -4,6 +4,8 @@
   - the EVM ecRecover precompile (Precompiled.cpp:443-482);
   - many blocks' tx / receipt roots in one call (BlockImpl.h:111-183), incl. empty and 1-tx blocks.
 All bit-exact against the oracle (tests/golden vectors pin the oracle itself).
+The secp256k1 known-key verify's decisions that signed and edited rows never reach (x(Q) >= n, s at (n - 1) / 2,
+coordinates at p, hash >= n, a doubling as the final addition) are in tests/test_gpu_k1_verify_edges.py.
 """
 import numpy as np
 import pytest
