@@ -5,6 +5,7 @@
 // the mixed addition).
 #include "ecc_device.h"
 #include "ec26_trio.h"
+#include "pair_inv.h"
 
 namespace bcosgpu {
 
@@ -1656,8 +1657,52 @@ __device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const I
     }
 }
 
-// tx_verify_trio26_kernel, eight waves.  Waves 0..3 do only what the chains need: wave 0 r^-1 mod n and at
-// once u2 = s / r and its GLV split, waves 1 .. 3 the table of R' = (w x, w^2) between them (trio_table_shared,
+// pair_inv.h's Ops on a wave of lane trios: the row shifts are DPP fetches, the product FieldN1's, the
+// inversion modinv_trio (role 0's value in, the inverse on role 1 out, then two fetches take it to the trio's
+// other lanes).  Stamps: 6 = the products before the inversion are done, 10 = the inverse is there.
+struct PairOpsTrio {
+    const TrioLane& T;
+    int lane;
+    template <int CTRL>
+    __device__ __forceinline__ static void shift(fe& o, const fe& a) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o.v[q] = trio::dpp<CTRL>(a.v[q]);
+    }
+    __device__ __forceinline__ void right1(fe& o, const fe& a) const { shift<trio::kR1>(o, a); }
+    __device__ __forceinline__ void left1(fe& o, const fe& a) const { shift<trio::kL1>(o, a); }
+    __device__ __forceinline__ void left2(fe& o, const fe& a) const { shift<trio::kL2>(o, a); }
+    __device__ __forceinline__ void sel(fe& o, int roles, const fe& a, const fe& b) const {
+        const bool c = ((roles & kPairRole0) && T.r0) || ((roles & kPairRole1) && T.r1) || ((roles & kPairRole2) && T.r2);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o.v[q] = c ? a.v[q] : b.v[q];
+    }
+    // (the s_nop: a product's limbs may be the source of the next DPP fetch, see trio::dpp_fence)
+    __device__ __forceinline__ void mul(fe& o, const fe& a, const fe& b) const {
+        FieldN1::mul(o, a, b);
+        asm volatile("s_nop 1"
+                     : "+v"(o.v[0]), "+v"(o.v[1]), "+v"(o.v[2]), "+v"(o.v[3]), "+v"(o.v[4]), "+v"(o.v[5]), "+v"(o.v[6]),
+                       "+v"(o.v[7]));
+    }
+    __device__ __forceinline__ void inv(fe& o, const fe& x) const {
+        fe t, a, b;
+        modinv_trio<0, 1>(t, x, kMod30N1, T, lane);
+        shift<trio::kR1>(a, t);
+        shift<trio::kL1>(b, t);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o.v[q] = T.r1 ? t.v[q] : T.r0 ? a.v[q] : b.v[q];
+    }
+    __device__ __forceinline__ void stamp(int k) const {
+        if (k == kPairStampPre) {
+            COOP_T(6);
+        } else {
+            COOP_T(10);
+        }
+    }
+};
+
+// tx_verify_trio26_kernel, eight waves.  Waves 0..3 do only what the chains need: wave 0 the scalars of the
+// workgroup's txs in pairs (pair_inv.h: one inversion mod n per pair on a trio seat gives both u2 = s / r, whose
+// GLV split it posts, and then both r^-1), waves 1 .. 3 the table of R' = (w x, w^2) between them (trio_table_shared,
 // with K = Zc^2 w for phase D); each enters phase C behind the four flags of those.  Waves 4..7 are helpers
 // (trio_recover_helper): the digest, u1, the comb windows of u1 G and their sum, and the whole square root, all of it needed in phase D only.  A helper shares a SIMD with a
 // chain wave and takes the issue slots that a lone wave leaves empty (a gfx950 SIMD is 32 lanes wide: a
@@ -1696,36 +1741,46 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         bool ok = false;
         fe_zero(r);
         fe_zero(s);
-        if (active && (wave <= 3 || wave == 4 + 2)) ok = io.rsv(i, r, s, v);
+        if (wave != 0 && active && (wave <= 3 || wave == 4 + 2)) ok = io.rsv(i, r, s, v);
         if (helper) {
             trio_recover_helper(L, io, i, active, ok, r, v, tab, tab_bits, wave - 4, lane);
             COOP_T(1);
         } else {
-            if (wave == 0) {  // r^-1 (Montgomery form) for the helpers' u1, then the chains' scalars
-                if (!ok) {    // r = 1, s = 0 keep the arithmetic of the rejected lanes well defined
-                    fe_zero(r);
-                    r.v[0] = 1;
-                    fe_zero(s);
-                }
-                fe rm, rinv, u2, k1, k2;
-                FieldN1::from_plain(rm, r);
-                FieldInv<FieldN1>::inv_pipe(rinv, rm);
-                lds_store_fe(L.xrinv, rinv, lane);
-                lds_flag_post(&L.post[0]);
-                COOP_T(7);
-                FieldN1::mul(u2, s, rinv);
-                COOP_T(10);
+            if (wave == 0) {
+                // The chains' scalars, then r^-1 (Montgomery form) for the helpers' u1, on the wave's trio seats:
+                // seat tl takes txs tl (role 0) and tl + 20 (role 1) of the workgroup and inverts r_a r_b once
+                // (pair_inv.h).  A member that is absent or rejected enters as r = 1, s = 0, which leaves its
+                // partner's values exact.  Roles 0 and 1 store their tx's column; the other 24 lanes fill the
+                // columns 40 .. 63 of xrinv, which the helpers' idle lanes read, with R (what r = 1 gives).
+                const bool phantom = (lane & 15) == 15, member = !T.r2 && !phantom;
+                const int col = phantom ? 60 + (lane >> 4) : tl + (T.r1 ? 20 : T.r2 ? 40 : 0);
+                const uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * kTrioTxs + col;
+                if (member && i0 < n) ok = io.rsv(i0, r, s, v);
+                pair_enter(r, s, ok);
+                PairOpsTrio ops{T, lane};
+                fe u2, inv, rinv, k1, k2;
+                pair_scalars(u2, inv, r, s, ops);
                 bool neg1, neg2;
                 glv_split(k1, neg1, k2, neg2, u2);
                 COOP_T(11);
+                if (member) {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    L.k[0][q][lane] = k1.v[q];
-                    L.k[1][q][lane] = k2.v[q];
+                    for (int q = 0; q < 4; ++q) {
+                        L.k[0][q][col] = k1.v[q];
+                        L.k[1][q][col] = k2.v[q];
+                    }
+                    L.flags[col] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
                 }
-                L.flags[lane] = (ok ? 1u : 0u) | (neg1 ? 4u : 0u) | (neg2 ? 8u : 0u);
                 lds_flag_post(&L.spost[0]);
                 COOP_T(8);
+                // (the helpers are not urgent: their r^-1 is one more product level, after the scalars' post)
+                pair_rinv(rinv, inv, r, ops);
+                fe one;
+                fe_set(one, ParamN1::ONE);
+                fe_cmov(rinv, one, !member);
+                lds_store_fe(L.xrinv, rinv, col);
+                lds_flag_post(&L.post[0]);
+                COOP_T(7);
             } else {  // the table of R' on waves 1, 2, 3 (trio_table_shared), each from its own r, v
                 fe26 X, rhs, beta;
                 recover_w(X, rhs, r, v, ok);

@@ -54,15 +54,21 @@ __global__ __launch_bounds__(256, OCC) void tx_verify_kernel(IO io, uint64_t n, 
 // the pair kernels 64, the one-lane kernel 256 at occupancy 1 (one wave per SIMD) and 512 at
 // occupancy 2 -- and a round costs a fixed latency, so a kernel's cost is rounds x latency.  The
 // occupancy-2 kernel's last round, when it leaves every SIMD at most one wave, has its own (shorter)
-// latency.  Latencies relative to the trio kernel's round, fitted from the round-4 sweep on MI355X
+// latency.  The unit of every latency below is the trio kernel's round AS THE ROUND-4 SWEEP MEASURED IT
 // (tools/small_sweep.py -> tools/fit_auto.py, profiles/r04_small_sweep.json and _fit.json): secp256k1
 // trio 0.379 / pair 0.485 / one-lane 1.00 (occupancy 1) / 1.70 (occupancy 2) / 0.97 ms (its single-wave
-// round); SM2 0.593 / 0.996 / 1.42 / 2.56 / 1.455 ms.  The trio and pair kernels are candidates up to
+// round); SM2 0.593 / 0.996 / 1.42 / 2.56 / 1.455 ms.  The secp256k1 trio kernel has become faster since, the
+// others have not (profiles/r07_small_sweep.json and _fit.json: trio 0.302 / pair 0.500 / one-lane 0.986 / 1.70 /
+// 0.972 ms), so its round now costs kTrioRoundK1 = 0.302 / 0.379 of that unit, and the tables keep their
+// values (bench.py's mirror of them, which only labels its roofline, has no such factor; the two agree at every
+// size the benchmark runs).  The trio and pair kernels are candidates up to
 // 2^16 txs (beyond that the one-lane kernel's throughput wins at any rounding).  secp256k1 recovery also
 // has the row kernel (ecc_row.hip, one signature per workgroup): its first round of one signature per
 // CU costs kRowLat of the trio's round and each further round kRowLatN (two workgroups share a CU:
 // tools/small_sweep.py, profiles/r05_small_sweep_row.json: 0.127 / 0.153 / 0.211 / 0.280 / 0.347 ms at
-// 1 / 256 / 512 / 768 / 1024 signatures against the trio's 0.378); SM2 its own row kernel, at
+// 1 / 256 / 512 / 768 / 1024 signatures against the trio's 0.378 then; profiles/r07_small_sweep_row.json: 0.127 /
+// 0.140 / 0.210 / 0.281 / 0.347 ms, a line of 0.140 + 0.069 per further signature = 0.37 + 0.18 of the unit,
+// against the trio's 0.301 now, which wins from 1,024 signatures on instead of 1,280); SM2 its own row kernel, at
 // kRowLatSM2 for one signature per CU and kRowLatNSM2 per further one while kRowResidentSM2 workgroups
 // share a CU, a new round beyond (same file: 0.221 / 0.250 / 0.384 / 0.401 / 0.485 / 0.754 ms at 1 / 256 /
 // 512 / 768 / 1024 / 1280 signatures against the trio's 0.578).
@@ -70,6 +76,7 @@ __global__ __launch_bounds__(256, OCC) void tx_verify_kernel(IO io, uint64_t n, 
 static constexpr double kRowLat = 0.38, kRowLatN = 0.18;
 static constexpr double kRowLatSM2 = 0.43, kRowLatNSM2 = 0.14;
 static constexpr uint64_t kRowResidentSM2 = 4;
+static constexpr double kTrioRoundK1 = 0.796;  // the secp256k1 trio kernel's round today, in the tables' unit
 static int auto_kernel(int suite, uint64_t n, int cus, bool small_ok, bool row_ok) {
     const bool sm2 = suite == BCOSGPU_SUITE_SM2;
     //                    occ 2,              occ 1,              pair,               trio
@@ -81,6 +88,7 @@ static int auto_kernel(int suite, uint64_t n, int cus, bool small_ok, bool row_o
     double cost = 1e300;
     for (int k = small_ok ? 3 : 1; k >= 0; --k) {
         double c = static_cast<double>((n + per[k] - 1) / per[k]) * lat[k];
+        if (k == 3 && !sm2) c *= kTrioRoundK1;
         if (k == 0) {  // occupancy 2: full rounds, then a tail round
             const uint64_t tail = n % per[0];
             c = static_cast<double>(n / per[0]) * lat[0] + (tail == 0 ? 0.0 : tail <= per[1] ? occ2_tail : lat[0]);

@@ -367,8 +367,9 @@ struct FieldInv<FieldN1> {
         mont_inv_safegcd<ParamN1, 2>(r, a, kMod30N1, kR3N1);
     }
     // as FieldInv<FieldK1>::inv_trio, Montgomery form in and out (the product with R^3 on every lane; role
-    // DST's is the inverse).  No kernel calls it: the recovery kernel's phase A on trio seats measured slower
-    //  and keeps inv_pipe.  tools/invbench.hip compares it with inv_pipe on a wave of 20 values.
+    // DST's is the inverse).  No kernel calls it: the recovery kernel's phase A inverts the product of a tx
+    // pair's r with modinv_trio itself and its one correction is a product with R^2 (pair_inv.h).
+    // tools/invbench.hip compares it with inv_pipe on a wave of 20 values.
     template <int SRC, int DST>
     __device__ static __forceinline__ void inv_trio(fe& r, const fe& a, const TrioLane& T, int lane) {
         fe t, k;

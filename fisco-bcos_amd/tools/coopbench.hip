@@ -1,7 +1,8 @@
 // coopbench.hip -- phase timestamps (s_memtime cycles) of tx_verify_coop_kernel's (argv[1] = 26:
 // tx_verify_coop26_kernel's, trio: tx_verify_trio26_kernel's) workgroup 0 on a
 // 10k-tx batch of random inputs (the schedule is input-independent), to see where C2's latency goes.
-// trio prints eight waves (0..3 the chains, 4..7 the helpers): r^-1 / u2 / split / scalars posted on wave 0, the
+// trio prints eight waves (0..3 the chains, 4..7 the helpers): the tx pairs' products before the inversion / the
+// inversion / split / scalars posted / r^-1 posted on wave 0, the
 // table's hand-offs on waves 1 .. 3, chain start and
 // phase C per chain wave, the Z^-1, each helper's last result posted, kernel end.
 #define BCOSGPU_COOP_TIMING 1
@@ -66,8 +67,9 @@ int main(int argc, char** argv) {
         for (int w = 0; w < 8; ++w) {
             printf("%s\"wave%d\": {\"start\": %lld, \"phase_a_work_end\": %lld", w ? ", " : "", w, at(w, 0), at(w, 1));
             if (w == 0)
-                printf(", \"rinv_posted\": %lld, \"u2_done\": %lld, \"split_done\": %lld, \"scalars_posted\": %lld", at(w, 7),
-                       at(w, 10), at(w, 11), at(w, 8));
+                printf(", \"pre_products_done\": %lld, \"inversion_done\": %lld, \"split_done\": %lld, "
+                       "\"scalars_posted\": %lld, \"rinv_posted\": %lld",
+                       at(w, 6), at(w, 10), at(w, 11), at(w, 8), at(w, 7));
             // the table on waves 1 .. 3 (trio_table_shared): wave 1 and 3 their multiples, wave 2 the prefix products
             // and Zc, wave 1 the suffix products, each its entries ("table_posted": its "done" flag)
             if (w == 1 || w == 3) printf(", \"multiples_posted\": %lld", at(w, 10));
