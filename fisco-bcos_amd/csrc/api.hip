@@ -7,6 +7,7 @@
 #include <vector>
 #include <cstring>
 #include "engine.h"
+#include "consensus_stage.h"
 
 using namespace bcosgpu;
 
@@ -590,57 +591,21 @@ int bcosgpu_cbc_decrypt_batch(int cipher_id, const uint8_t* key, size_t key_len,
 // ------------------------------------------------------------------ signature rows against a consensus set
 namespace {
 
-// The signature rows of a check against a consensus set (block headers, PBFT messages): a row is a node index
-// and a signature, verified against that node's key and counted with that node's weight.  The consensus keys
-// are registered (a cached key is a lookup); with ids for all of them the rows carry slot ids, otherwise the
-// keys.  A row whose index names no consensus node (ConsensusConfig.cpp:150-158), or whose signature is shorter
-// than verify accepts (bcos_gpu.hpp:94-115), fails without a key: a negative id, or a zero key, and a zero
-// signature.  Constructed after the call's WsCall (the device is initialised by then).
-struct ConsensusRows {
+// The device half of a check's signature rows (ConsensusRows, consensus_stage.h, is the host half): the consensus
+// keys are registered (a cached key is a lookup) and their slot ids handed to the stage's plan; no rows, or an
+// empty set, registers nothing.  Constructed after the call's WsCall (the device is initialised by then).
+struct ConsensusKeys {
     const int suite;
-    const bcosgpu_ConsensusSet& cs;
-    const uint64_t rows;
     const uint64_t gen;          // the key cache's generation before the registration
-    bool keyed;                  // the rows carry slot ids
-    std::vector<int32_t> slots;  // of the consensus keys
-    std::vector<int32_t> node;   // the consensus node of each row, -1 = the row fails without a key
-    std::vector<uint8_t> pubs;   // the rows' keys, when the run has to be repeated
-    uint8_t* sig = nullptr;      // staging of the rows: r || s [64 rows], weights [rows], slot ids or keys
-    uint64_t* weight = nullptr;
-    uint8_t* key = nullptr;
-
-    ConsensusRows(int suite_, const bcosgpu_ConsensusSet& cs_, uint64_t rows_)
-        : suite(suite_), cs(cs_), rows(rows_), gen(keyed_generation(suite_)), keyed(rows_ != 0 && cs_.n != 0),
-          slots(cs_.n, -1), node(rows_, -1) {  // (an empty set registers nothing: its rows all fail, without keys)
-        if (keyed && keyed_register(suite, cs.node_ids64, cs.n, slots.data())) {
+    std::vector<int32_t> slots;  // of the consensus keys, -1 = none
+    ConsensusKeys(int suite_, const bcosgpu_ConsensusSet& cs, uint64_t rows)
+        : suite(suite_), gen(keyed_generation(suite_)), slots(cs.n, -1) {
+        if (rows && cs.n && keyed_register(suite, cs.node_ids64, cs.n, slots.data())) {
             (void)hipGetLastError();  // a failed table build leaves the key path
-            keyed = false;
+            slots.assign(cs.n, -1);
         }
-        for (size_t k = 0; keyed && k < cs.n; ++k) keyed = slots[k] >= 0;
-    }
-    uint64_t key_bytes() const { return keyed ? 4 * rows : 64 * rows; }
-    void stage(uint8_t* sig_, uint64_t* weight_, uint8_t* key_) {
-        sig = sig_, weight = weight_, key = key_;
-        std::memset(sig, 0, 64 * rows);
-        if (!keyed) std::memset(key, 0, 64 * rows);
-    }
-    bool known(int64_t index) const { return index >= 0 && static_cast<uint64_t>(index) < cs.n; }
-    void put(uint64_t r, int64_t index, const uint8_t* signature, size_t signature_len) {
-        const bool ok = known(index) && signature_len >= 64;
-        const int32_t k = ok ? static_cast<int32_t>(index) : -1;
-        node[r] = k;
-        weight[r] = ok ? cs.weights[k] : 0;
-        if (ok) std::memcpy(sig + 64 * r, signature, 64);
-        if (keyed) reinterpret_cast<int32_t*>(key)[r] = ok ? slots[k] : -1;
-        else if (ok) std::memcpy(key + 64 * r, cs.node_ids64 + 64 * k, 64);
     }
     bool stale() const { return keyed_generation(suite) != gen; }
-    const uint8_t* row_pubs() {
-        pubs.assign(64 * rows, 0);
-        for (uint64_t q = 0; q < rows; ++q)
-            if (node[q] >= 0) std::memcpy(pubs.data() + 64 * q, cs.node_ids64 + 64 * node[q], 64);
-        return pubs.data();
-    }
 };
 
 int check_consensus_set(const bcosgpu_ConsensusSet& cs) {
@@ -649,16 +614,20 @@ int check_consensus_set(const bcosgpu_ConsensusSet& cs) {
     return 0;
 }
 
-// Runs `enqueue` (the kernels over the arguments `a` and the download, on c's stream; 0, or an error that is
-// already set) and waits for it.  If the key cache was cleared (bcosgpu_clear_keys) between the registration
-// and here, the ids may name other keys' tables by now: the run is repeated once with the keys in the rows (as
-// coalesce.hip does), uploaded into workspace buffer 3.
-template <class Args, class Enqueue>
-int run_rows(WsCall& c, ConsensusRows& cr, Args& a, Enqueue enqueue) {
+// Runs the check's kernels over the arguments `a` (`launch`: launch_headers_check or launch_pbft_check) and the
+// download of the out_bytes at dout into ho, on c's stream, and waits for them.  If the key cache was cleared
+// (bcosgpu_clear_keys) between the registration and here, the ids may name other keys' tables by now: the run
+// is repeated once with the keys in the rows (as coalesce.hip does), uploaded into workspace buffer 3.
+template <class Args, class Launch>
+int run_rows(WsCall& c, const ConsensusKeys& keys, ConsensusRows& cr, Args& a, Launch launch, const char* what,
+             uint8_t* ho, const uint8_t* dout, uint64_t out_bytes) {
     for (int attempt = 0; attempt < 2; ++attempt) {
-        if (int rc = enqueue()) return rc;
+        const int rc = launch(keys.suite, a, c.stream());
+        if (rc == BCOSGPU_E_ARG) return set_err(rc, "batch too large");
+        if (rc) return hip_err(hipGetLastError(), what);
+        HIP_OK(hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, c.stream()));
         HIP_OK(hipStreamSynchronize(c.stream()));
-        if (!a.d_row_slot || !cr.stale()) break;
+        if (!a.d_row_slot || !keys.stale()) break;
         HIP_OK(c.w->b[3].ensure(64 * cr.rows));
         HIP_OK(c.h2d(3, cr.row_pubs(), 64 * cr.rows));
         a.d_row_slot = nullptr, a.d_row_pub64 = c.buf(3);
@@ -702,25 +671,9 @@ int bcosgpu_headers_check_dev(int suite, const uint8_t* d_pre, const uint64_t* d
     return rc ? hip_err(hipGetLastError(), "headers check launch") : 0;
 }
 
-// The host-side part of asyncCheckBlock for one header (BlockValidator.cpp:35-63 with
-// checkSealerListAndWeightList, :80-139): the early verdict, 0 = go on to the signature rows.
-static uint8_t header_pre_status(const bcosgpu_BlockHeaderData& h, const bcosgpu_ConsensusSet& cs) {
-    if (h.block_number == 0) return BCOSGPU_HEADER_GENESIS;                         // :35-39
-    if (h.block_number <= cs.committed_index) return BCOSGPU_HEADER_E_COMMITTED;    // :49-53
-    if (h.tx_count == 0) return BCOSGPU_HEADER_NO_TXS;                              // :54-58
-    if (h.sealer < 0 || static_cast<uint64_t>(h.sealer) >= cs.n) return BCOSGPU_HEADER_E_SEALER;  // :85-93
-    if (h.nsealer_list != cs.n || h.nconsensus_weights != cs.n) return BCOSGPU_HEADER_E_SEALER_LIST;  // :98-108
-    for (size_t k = 0; k < cs.n; ++k) {                                             // :110-137
-        const bcosgpu_Bytes& id = h.sealer_list[k];
-        if (id.len != 64 || std::memcmp(id.data, cs.node_ids64 + 64 * k, 64) != 0) return BCOSGPU_HEADER_E_SEALER_LIST;
-        if (static_cast<uint64_t>(h.consensus_weights[k]) != cs.weights[k]) return BCOSGPU_HEADER_E_SEALER_LIST;
-    }
-    return 0;
-}
-
 // BlockValidator::asyncCheckBlock and the ledger's parent check for a run of headers (see bcos_gpu.h): the
 // early verdicts and the rows' keys and weights on the host, everything packed into pinned staging as one
-// block (64-bit arrays first, the preimages last), one H2D, the three phases, one D2H.
+// block (HeadersStage, consensus_stage.h), one H2D, the three phases, one D2H.
 int bcosgpu_headers_check(int suite, const bcosgpu_BlockHeaderData* headers, size_t n,
                           const bcosgpu_ConsensusSet* consensus, const uint8_t* prev_hash32_or_null,
                           int64_t prev_number, int flags, uint8_t* hash32, uint8_t* check, uint8_t* link,
@@ -730,112 +683,26 @@ int bcosgpu_headers_check(int suite, const bcosgpu_BlockHeaderData* headers, siz
     if (!headers || !consensus || !hash32 || !check || !link) return set_err(BCOSGPU_E_ARG, "null pointer");
     const bcosgpu_ConsensusSet& cs = *consensus;
     if (int rc = check_consensus_set(cs)) return rc;
-    // bad views first (the packer checks the hashed fields again; it does not see the signatures)
-    for (size_t i = 0; i < n; ++i) {
-        const bcosgpu_BlockHeaderData& h = headers[i];
-        if ((!h.signatures && h.nsignatures) || (!h.sealer_list && h.nsealer_list) ||
-            (!h.consensus_weights && h.nconsensus_weights) || (!h.parents && h.nparents) ||
-            (h.data_hash_len && (!h.data_hash || h.data_hash_len > 32)))
-            return set_err(BCOSGPU_E_ARG, "bad header view (null field with a length, or a dataHash over 32 bytes)");
-        for (size_t k = 0; k < h.nsealer_list; ++k)
-            if (!h.sealer_list[k].data && h.sealer_list[k].len) return set_err(BCOSGPU_E_ARG, "bad header view");
-        for (size_t s = 0; s < h.nsignatures; ++s)
-            if (!h.signatures[s].signature && h.signatures[s].signature_len)
-                return set_err(BCOSGPU_E_ARG, "bad header view (null signature with a length)");
-    }
-    std::vector<uint8_t> pre_status(n);
-    uint64_t rows = 0;
-    for (size_t i = 0; i < n; ++i)
-        if (!(pre_status[i] = header_pre_status(headers[i], cs))) rows += headers[i].nsignatures;
+    HeadersStage st{headers, n, cs, prev_hash32_or_null, prev_number, flags};
+    if (const char* bad = st.validate()) return set_err(BCOSGPU_E_ARG, bad);
     WsCall c;
     if (c.rc) return c.rc;
     Workspace* w = c.w;
-    ConsensusRows cr(suite, cs, rows);
-    const uint64_t pre_bytes = bcosgpu_header_preimage_size(headers, n, flags);
-    uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 7) & ~uint64_t{7};
-        return o;
-    };
-    const uint64_t o_pre_off = take(8 * (n + 1)), o_sig_off = take(8 * (n + 1)), o_number = take(8 * n),
-                   o_pnum = take(8 * n), o_weight = take(8 * rows), o_phash = take(32 * n), o_given = take(32 * n),
-                   o_prev = take(32), o_sig = take(64 * rows), o_key = take(cr.key_bytes()),
-                   o_mask = take(n), o_status = take(n), o_pok = take(n), o_pre = take(pre_bytes);
-    const uint64_t total = at;
-    HIP_OK(w->h[0].ensure(total + 16));
+    const ConsensusKeys keys(suite, cs, st.rows);
+    st.plan(keys.slots);
+    const HeadersStage::Plan& p = st.p;
+    HIP_OK(w->h[0].ensure(p.total + 16));
     uint8_t* hs = w->h[0].as<uint8_t>();
-    uint64_t* pre_off = reinterpret_cast<uint64_t*>(hs + o_pre_off);
-    if (bcosgpu_pack_header_preimages(headers, n, flags, hs + o_pre, pre_bytes, pre_off))
-        return set_err(BCOSGPU_E_ARG, "bad header view (null field with a length, a dataHash over 32 bytes, or a header "
-                                      "of 4 GiB or more)");
-    uint64_t* sig_off = reinterpret_cast<uint64_t*>(hs + o_sig_off);
-    int64_t* number = reinterpret_cast<int64_t*>(hs + o_number);
-    int64_t* pnum = reinterpret_cast<int64_t*>(hs + o_pnum);
-    cr.stage(hs + o_sig, reinterpret_cast<uint64_t*>(hs + o_weight), hs + o_key);
-    std::memset(hs + o_phash, 0, 64 * n);  // parent hashes, given hashes
-    if (prev_hash32_or_null) std::memcpy(hs + o_prev, prev_hash32_or_null, 32);
-    uint64_t r = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const bcosgpu_BlockHeaderData& h = headers[i];
-        number[i] = h.block_number;
-        const bool pok = h.nparents && h.parents[0].block_hash_len == 32;  // LedgerImpl.h:302-306 reads [0] only
-        pnum[i] = h.nparents ? h.parents[0].block_number : 0;
-        hs[o_pok + i] = pok;
-        if (pok) std::memcpy(hs + o_phash + 32 * i, h.parents[0].block_hash, 32);
-        const bool given = h.data_hash_len && !(flags & BCOSGPU_HEADER_RECOMPUTE);  // TarsHashable.h:81-85
-        hs[o_mask + i] = given;
-        if (given) std::memcpy(hs + o_given + 32 * i, h.data_hash, h.data_hash_len);
-        hs[o_status + i] = pre_status[i];
-        sig_off[i] = r;
-        if (pre_status[i]) continue;
-        for (size_t s = 0; s < h.nsignatures; ++s, ++r)
-            cr.put(r, h.signatures[s].sealer_index, h.signatures[s].signature, h.signatures[s].signature_len);
-    }
-    sig_off[n] = r;
-    const uint64_t work = headers_check_work_bytes(n, rows);
-    const uint64_t out_ok = (34 * n + 7) & ~uint64_t{7}, out_bytes = out_ok + rows;
-    HIP_OK(w->h[1].ensure(out_bytes + 16));
-    HIP_OK(c.ensure({total + 16, work, out_bytes + 16}));
-    HIP_OK(c.h2d(0, hs, total));
-    const uint8_t* di = c.buf(0);
-    uint8_t* dout = c.buf(2);
+    if (const char* bad = st.pack(hs)) return set_err(BCOSGPU_E_ARG, bad);
+    const uint64_t work = headers_check_work_bytes(n, st.rows);
+    HIP_OK(w->h[1].ensure(p.out_bytes + 16));
+    HIP_OK(c.ensure({p.total + 16, work, p.out_bytes + 16}));
+    HIP_OK(c.h2d(0, hs, p.total));
     uint8_t* ho = w->h[1].as<uint8_t>();
-    HeadersCheckArgs a;
-    a.d_pre = di + o_pre, a.d_pre_off = reinterpret_cast<const uint64_t*>(di + o_pre_off);
-    a.d_given32 = di + o_given, a.d_given_mask = di + o_mask, a.d_pre_status = di + o_status;
-    a.d_number = reinterpret_cast<const int64_t*>(di + o_number);
-    a.d_parent_number = reinterpret_cast<const int64_t*>(di + o_pnum);
-    a.d_parent_hash32 = di + o_phash, a.d_parent_ok = di + o_pok;
-    a.d_prev_hash32 = prev_hash32_or_null ? di + o_prev : nullptr, a.prev_number = prev_number;
-    a.d_sig_off = reinterpret_cast<const uint64_t*>(di + o_sig_off), a.d_sig = di + o_sig;
-    a.d_row_weight = reinterpret_cast<const uint64_t*>(di + o_weight);
-    if (cr.keyed) a.d_row_slot = reinterpret_cast<const int32_t*>(di + o_key);
-    else a.d_row_pub64 = di + o_key;
-    a.quorum = cs.min_required_quorum, a.n = n, a.rows = rows;
-    a.d_hash32 = dout, a.d_check = dout + 32 * n, a.d_link = dout + 33 * n, a.d_sig_ok = dout + out_ok;
-    a.d_work = c.buf<void>(1), a.work_bytes = work;
-    const int run = run_rows(c, cr, a, [&]() -> int {
-        const int rc = launch_headers_check(suite, a, c.stream());
-        if (rc == BCOSGPU_E_ARG) return set_err(rc, "batch too large");
-        if (rc) return hip_err(hipGetLastError(), "headers check launch");
-        HIP_OK(hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, c.stream()));
-        return 0;
-    });
-    if (run) return run;
+    HeadersCheckArgs a = st.args(c.buf(0), c.buf(2), c.buf<void>(1), work);
+    if (int rc = run_rows(c, keys, st.cr, a, launch_headers_check, "headers check launch", ho, c.buf(2), p.out_bytes)) return rc;
     if (int rc = c.finish()) return rc;
-    std::memcpy(hash32, ho, 32 * n);
-    std::memcpy(check, ho + 32 * n, n);
-    std::memcpy(link, ho + 33 * n, n);
-    if (sig_ok_or_null) {  // rows -> one entry per signature; 2 = the header's signatures were not checked
-        uint64_t s = 0, q = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const size_t m = headers[i].nsignatures;
-            if (pre_status[i]) std::memset(sig_ok_or_null + s, 2, m);
-            else if (m) std::memcpy(sig_ok_or_null + s, ho + out_ok + q, m), q += m;
-            s += m;
-        }
-    }
+    st.scatter(ho, hash32, check, link, sig_ok_or_null);
     return 0;
 }
 
@@ -873,27 +740,10 @@ int bcosgpu_pbft_check_dev(int suite, const uint8_t* d_data, const uint64_t* d_d
     return rc ? hip_err(hipGetLastError(), "pbft check launch") : 0;
 }
 
-// A field of a view: a null pointer with a length, or (hashes) more than 32 bytes, is a bad view.
-static bool bad_field(const uint8_t* p, size_t len, size_t max_len = ~size_t{0}) { return (!p && len) || len > max_len; }
-
-static bool bad_pbft_view(const bcosgpu_PBFTMessageData& m) {
-    if (bad_field(m.signed_data, m.signed_data_len, 0xFFFFFFFEull) || bad_field(m.signature_hash, m.signature_hash_len, 32) ||
-        bad_field(m.signature, m.signature_len) || bad_field(m.proposal_hash, m.proposal_hash_len, 32) ||
-        bad_field(m.proposal_signature, m.proposal_signature_len) || (!m.prepared && m.nprepared))
-        return true;
-    for (size_t p = 0; p < m.nprepared; ++p) {
-        const bcosgpu_PrecommitProof& pp = m.prepared[p];
-        if (bad_field(pp.hash, pp.hash_len, 32) || (!pp.proofs && pp.nproofs)) return true;
-        for (size_t s = 0; s < pp.nproofs; ++s)
-            if (bad_field(pp.proofs[s].signature, pp.proofs[s].signature_len)) return true;
-    }
-    return false;
-}
-
 // The signature checks of a drained PBFT message queue (see bcos_gpu.h): every requested signature becomes a
 // row (the proofs of all prepared proposals first, then the message and proposal signatures) with its node's
-// key and weight, everything packed into pinned staging as one block (64-bit arrays first, the
-// signed data last), one H2D, the four phases, one D2H.
+// key and weight, everything packed into pinned staging as one block (PbftStage, consensus_stage.h), one H2D,
+// the four phases, one D2H.
 int bcosgpu_pbft_check(int suite, const bcosgpu_PBFTMessageData* msgs, size_t n, const bcosgpu_PBFTGroup* groups,
                        size_t ngroups, const bcosgpu_ConsensusSet* consensus, int flags, uint8_t* msg_hash32,
                        uint32_t* msg_flags, uint8_t* prepared_check_or_null, uint8_t* sig_ok_or_null) {
@@ -904,138 +754,26 @@ int bcosgpu_pbft_check(int suite, const bcosgpu_PBFTMessageData* msgs, size_t n,
         return set_err(BCOSGPU_E_ARG, "null pointer");
     const bcosgpu_ConsensusSet& cs = *consensus;
     if (int rc = check_consensus_set(cs)) return rc;
-    // the rows: the proofs of every checked prepared proposal first, in order (the CSR of the verdict kernel),
-    // then the message and proposal signatures
-    uint64_t proof_rows = 0, sig_rows = 0, nprep = 0, data_bytes = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const bcosgpu_PBFTMessageData& m = msgs[i];
-        if (bad_pbft_view(m))
-            return set_err(BCOSGPU_E_ARG, "bad PBFT message view (null field with a length, a hash over 32 bytes, or "
-                                          "signed data of 4 GiB or more)");
-        sig_rows += (m.checks & BCOSGPU_PBFT_CHECK_MSG_SIG) != 0;
-        sig_rows += (m.checks & BCOSGPU_PBFT_CHECK_PROPOSAL_SIG) && m.proposal_signature_len;  // absent: no row (:755-758)
-        for (size_t p = 0; p < m.nprepared && (m.checks & BCOSGPU_PBFT_CHECK_PREPARED); ++p)
-            proof_rows += m.prepared[p].nproofs;
-        nprep += m.nprepared;
-        if (!m.signature_hash_len) data_bytes += m.signed_data_len;
-    }
-    const uint64_t rows = proof_rows + sig_rows;
-    for (size_t g = 0; g < ngroups; ++g)
-        if (groups[g].parent >= n || groups[g].first > n || groups[g].count > n - groups[g].first)
-            return set_err(BCOSGPU_E_ARG, "a group names messages outside [0, n)");
+    PbftStage st{msgs, n, groups, ngroups, cs};
+    if (const char* bad = st.validate()) return set_err(BCOSGPU_E_ARG, bad);
     WsCall c;
     if (c.rc) return c.rc;
     Workspace* w = c.w;
-    ConsensusRows cr(suite, cs, rows);
-    uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 7) & ~uint64_t{7};
-        return o;
-    };
-    const uint64_t o_data_off = take(8 * (n + 1)), o_mweight = take(8 * n), o_mrow = take(8 * n), o_prow = take(8 * n),
-                   o_prep_off = take(8 * (n + 1)), o_prep_row = take(8 * (nprep + 1)), o_groups = take(24 * ngroups),
-                   o_weight = take(8 * rows), o_given = take(32 * n), o_rhash = take(32 * rows), o_sig = take(64 * rows),
-                   o_key = take(cr.key_bytes()), o_mask = take(n), o_pre = take(n), o_checks = take(n),
-                   o_data = take(data_bytes);
-    const uint64_t total = at;
-    HIP_OK(w->h[0].ensure(total + 16));
+    const ConsensusKeys keys(suite, cs, st.rows);
+    st.plan(keys.slots);
+    const PbftStage::Plan& p = st.p;
+    HIP_OK(w->h[0].ensure(p.total + 16));
     uint8_t* hs = w->h[0].as<uint8_t>();
-    uint64_t* data_off = reinterpret_cast<uint64_t*>(hs + o_data_off);
-    uint64_t* mweight = reinterpret_cast<uint64_t*>(hs + o_mweight);
-    int64_t* mrow = reinterpret_cast<int64_t*>(hs + o_mrow);
-    int64_t* prow = reinterpret_cast<int64_t*>(hs + o_prow);
-    uint64_t* prep_off = reinterpret_cast<uint64_t*>(hs + o_prep_off);
-    uint64_t* prep_row = reinterpret_cast<uint64_t*>(hs + o_prep_row);
-    cr.stage(hs + o_sig, reinterpret_cast<uint64_t*>(hs + o_weight), hs + o_key);
-    std::memset(hs + o_given, 0, 32 * n);
-    std::memset(hs + o_rhash, 0, 32 * rows);
-    uint64_t q = 0, r = proof_rows, p = 0, d = 0;  // the next proof row, the next signature row
-    for (size_t i = 0; i < n; ++i) {
-        const bcosgpu_PBFTMessageData& m = msgs[i];
-        const bool known = cr.known(m.generated_from);
-        hs[o_pre + i] = known ? 0 : BCOSGPU_PBFT_E_NODE;  // PBFTEngine.cpp:735-741, :759-767
-        hs[o_checks + i] = static_cast<uint8_t>(m.checks & 7u);
-        mweight[i] = known ? cs.weights[m.generated_from] : 0;
-        hs[o_mask + i] = m.signature_hash_len != 0;
-        data_off[i] = d;
-        if (m.signature_hash_len) std::memcpy(hs + o_given + 32 * i, m.signature_hash, m.signature_hash_len);
-        else if (m.signed_data_len) std::memcpy(hs + o_data + d, m.signed_data, m.signed_data_len), d += m.signed_data_len;
-        mrow[i] = prow[i] = -1;
-        if (m.checks & BCOSGPU_PBFT_CHECK_MSG_SIG) {  // the hash kernel writes this row's hash
-            cr.put(r, m.generated_from, m.signature, m.signature_len);
-            mrow[i] = static_cast<int64_t>(r++);
-        }
-        if ((m.checks & BCOSGPU_PBFT_CHECK_PROPOSAL_SIG) && m.proposal_signature_len) {
-            cr.put(r, m.generated_from, m.proposal_signature, m.proposal_signature_len);
-            if (m.proposal_hash_len) std::memcpy(hs + o_rhash + 32 * r, m.proposal_hash, m.proposal_hash_len);
-            prow[i] = static_cast<int64_t>(r++);
-        }
-        prep_off[i] = p;
-        for (size_t k = 0; k < m.nprepared; ++k, ++p) {
-            const bcosgpu_PrecommitProof& pp = m.prepared[k];
-            prep_row[p] = q;
-            for (size_t s = 0; s < pp.nproofs && (m.checks & BCOSGPU_PBFT_CHECK_PREPARED); ++s, ++q) {
-                cr.put(q, pp.proofs[s].sealer_index, pp.proofs[s].signature, pp.proofs[s].signature_len);
-                if (pp.hash_len) std::memcpy(hs + o_rhash + 32 * q, pp.hash, pp.hash_len);
-            }
-        }
-    }
-    data_off[n] = d, prep_off[n] = p, prep_row[nprep] = q;
-    for (size_t g = 0; g < ngroups; ++g) {
-        uint64_t* t = reinterpret_cast<uint64_t*>(hs + o_groups) + 3 * g;
-        t[0] = groups[g].parent, t[1] = groups[g].first, t[2] = groups[g].count;
-    }
-    const uint64_t work = pbft_check_work_bytes(n, rows);
-    const uint64_t out_prep = 36 * n, out_ok = (out_prep + nprep + 7) & ~uint64_t{7}, out_bytes = out_ok + rows;
-    HIP_OK(w->h[1].ensure(out_bytes + 16));
-    HIP_OK(c.ensure({total + 16, work, out_bytes + 16}));
-    HIP_OK(c.h2d(0, hs, total));
-    uint8_t* di = c.buf(0);
-    uint8_t* dout = c.buf(2);
+    st.pack(hs);
+    const uint64_t work = pbft_check_work_bytes(n, st.rows);
+    HIP_OK(w->h[1].ensure(p.out_bytes + 16));
+    HIP_OK(c.ensure({p.total + 16, work, p.out_bytes + 16}));
+    HIP_OK(c.h2d(0, hs, p.total));
     uint8_t* ho = w->h[1].as<uint8_t>();
-    PbftCheckArgs a;
-    a.d_data = di + o_data, a.d_data_off = reinterpret_cast<const uint64_t*>(di + o_data_off);
-    a.d_given32 = di + o_given, a.d_given_mask = di + o_mask, a.d_pre_flags = di + o_pre, a.d_checks = di + o_checks;
-    a.d_msg_weight = reinterpret_cast<const uint64_t*>(di + o_mweight);
-    a.d_msg_row = reinterpret_cast<const int64_t*>(di + o_mrow), a.d_prop_row = reinterpret_cast<const int64_t*>(di + o_prow);
-    a.d_prep_off = reinterpret_cast<const uint64_t*>(di + o_prep_off);
-    a.d_prep_row_off = reinterpret_cast<const uint64_t*>(di + o_prep_row), a.nprep = nprep;
-    a.d_row_hash32 = di + o_rhash, a.d_sig = di + o_sig, a.d_row_weight = reinterpret_cast<const uint64_t*>(di + o_weight);
-    if (cr.keyed) a.d_row_slot = reinterpret_cast<const int32_t*>(di + o_key);
-    else a.d_row_pub64 = di + o_key;
-    a.d_groups = reinterpret_cast<const uint64_t*>(di + o_groups), a.ngroups = ngroups;
-    a.quorum = cs.min_required_quorum, a.n = n, a.rows = rows;
-    a.d_msg_hash32 = dout, a.d_msg_flags = reinterpret_cast<uint32_t*>(dout + 32 * n);
-    a.d_prepared_check = dout + out_prep, a.d_sig_ok = dout + out_ok;
-    a.d_work = c.buf<void>(1), a.work_bytes = work;
-    const int run = run_rows(c, cr, a, [&]() -> int {
-        const int rc = launch_pbft_check(suite, a, c.stream());
-        if (rc == BCOSGPU_E_ARG) return set_err(rc, "batch too large");
-        if (rc) return hip_err(hipGetLastError(), "pbft check launch");
-        HIP_OK(hipMemcpyAsync(ho, dout, out_bytes, hipMemcpyDeviceToHost, c.stream()));
-        return 0;
-    });
-    if (run) return run;
+    PbftCheckArgs a = st.args(c.buf(0), c.buf(2), c.buf<void>(1), work);
+    if (int rc = run_rows(c, keys, st.cr, a, launch_pbft_check, "pbft check launch", ho, c.buf(2), p.out_bytes)) return rc;
     if (int rc = c.finish()) return rc;
-    std::memcpy(msg_hash32, ho, 32 * n);
-    std::memcpy(msg_flags, ho + 32 * n, 4 * n);
-    if (prepared_check_or_null && nprep) std::memcpy(prepared_check_or_null, ho + out_prep, nprep);
-    if (sig_ok_or_null) {  // rows -> per message: the message signature, the proposal signature, the proofs
-        const uint8_t* ok = ho + out_ok;
-        uint8_t* s = sig_ok_or_null;
-        for (size_t i = 0; i < n; ++i) {
-            const bcosgpu_PBFTMessageData& m = msgs[i];
-            *s++ = mrow[i] >= 0 ? ok[mrow[i]] : 2;
-            *s++ = prow[i] >= 0 ? ok[prow[i]] : (m.checks & BCOSGPU_PBFT_CHECK_PROPOSAL_SIG) ? 0 : 2;  // absent: failed
-            for (size_t k = 0; k < m.nprepared; ++k) {
-                const size_t cnt = m.prepared[k].nproofs;
-                if (m.checks & BCOSGPU_PBFT_CHECK_PREPARED) std::memcpy(s, ok + prep_row[prep_off[i] + k], cnt);
-                else std::memset(s, 2, cnt);
-                s += cnt;
-            }
-        }
-    }
+    st.scatter(hs, ho, msg_hash32, msg_flags, prepared_check_or_null, sig_ok_or_null);
     return 0;
 }
 
