@@ -149,35 +149,40 @@ F26_HD void sel_dpp2(E& r, bool c, const E& a, bool d, const E& b) {
 // r = c ? a : DPP<CTRL>(b) in one v_cndmask_b32_dpp per limb (the DPP combiner is off, so the fold
 // is written out): VCC = cm, the wave mask of c; s_nop 1 gives the DPP source its two wait states
 // after a VALU write (SALU -> VALU reads of VCC need none).  Five limbs per block (operand limit).
+// The mask is an input bound to VCC itself (a register variable): the compiler copies cm there in front
+// of a block only where VCC does not hold it already, so blocks of one role that follow each other share
+// one s_mov_b64 (the three role masks and their complements are kernel-long SGPR pairs).  The ten limbs'
+// second block carries no s_nop of its own: the first block's covers it unless the compiler puts a VALU
+// write of a limb of b between the two, which tools/hazard_check.py (tests/test_hazards.py) would find in
+// the built code.
 #define TRIO_CSEL_INS(D, S0, S1, CTL) "v_cndmask_b32_dpp %" #D ", %" #S0 ", %" #S1 ", vcc " CTL \
     " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define TRIO_CSEL5(CTL, r, a, b, o, cm)                                                                \
-    asm volatile("s_mov_b64 vcc, %15\n\ts_nop 1\n\t" TRIO_CSEL_INS(0, 10, 5, CTL) TRIO_CSEL_INS(1, 11, 6, CTL) \
+#define TRIO_CSEL5(NOP, CTL, r, a, b, o, cm)                                                            \
+    asm volatile(NOP TRIO_CSEL_INS(0, 10, 5, CTL) TRIO_CSEL_INS(1, 11, 6, CTL)                         \
                  TRIO_CSEL_INS(2, 12, 7, CTL) TRIO_CSEL_INS(3, 13, 8, CTL) TRIO_CSEL_INS(4, 14, 9, CTL)      \
                  : "=&v"((r).v[o]), "=&v"((r).v[o + 1]), "=&v"((r).v[o + 2]), "=&v"((r).v[o + 3]),       \
                    "=&v"((r).v[o + 4])                                                                  \
                  : "v"((a).v[o]), "v"((a).v[o + 1]), "v"((a).v[o + 2]), "v"((a).v[o + 3]), "v"((a).v[o + 4]), \
                    "v"((b).v[o]), "v"((b).v[o + 1]), "v"((b).v[o + 2]), "v"((b).v[o + 3]), "v"((b).v[o + 4]), \
-                   "s"(cm)                                                                              \
-                 : "vcc")
+                   "s"(cm))
+#define TRIO_CSEL10(CTL, r, a, b, cm)                    \
+    register uint64_t vcc_cm asm("vcc") = (cm);          \
+    TRIO_CSEL5("s_nop 1\n\t", CTL, r, a, b, 0, vcc_cm); \
+    TRIO_CSEL5("", CTL, r, a, b, 5, vcc_cm)
 template <int CTRL, class E>
 F26_HD void csel(E& r, bool c, uint64_t cm, const E& a, const E& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     (void)c;
     E t;
     if constexpr (CTRL == kL1) {
-        TRIO_CSEL5("row_shr:1", t, a, b, 0, cm);
-        TRIO_CSEL5("row_shr:1", t, a, b, 5, cm);
+        TRIO_CSEL10("row_shr:1", t, a, b, cm);
     } else if constexpr (CTRL == kL2) {
-        TRIO_CSEL5("row_shr:2", t, a, b, 0, cm);
-        TRIO_CSEL5("row_shr:2", t, a, b, 5, cm);
+        TRIO_CSEL10("row_shr:2", t, a, b, cm);
     } else if constexpr (CTRL == kR1) {
-        TRIO_CSEL5("row_shl:1", t, a, b, 0, cm);
-        TRIO_CSEL5("row_shl:1", t, a, b, 5, cm);
+        TRIO_CSEL10("row_shl:1", t, a, b, cm);
     } else {
         static_assert(CTRL == kR2, "csel: row shift by 1 or 2");
-        TRIO_CSEL5("row_shl:2", t, a, b, 0, cm);
-        TRIO_CSEL5("row_shl:2", t, a, b, 5, cm);
+        TRIO_CSEL10("row_shl:2", t, a, b, cm);
     }
     r = t;
 #else

@@ -1021,7 +1021,8 @@ struct Trio26RecoverLds : Trio26Lds {
     uint32_t sq[10][40];
     uint32_t yok[64];
     // The kernel runs eight waves: 0..3 the chains (wave w: chain w & 1 of txs 20 (w >> 1) .. + 19), 4..7
-    // the helpers (one lane per tx; helper h = wave - 4 shares a SIMD with wave h).  No barrier separates
+    // the helpers (one lane per tx; helpers 0, 1, 2, 3 run on waves 4, 5, 7, 6 and share a SIMD with chain
+    // waves 0, 1, 3, 2: trio_helper_of_wave).  No barrier separates
     // the phases up to phase D's first one, so the hand-offs are one-way flags (lds_flag_post: a release
     // store of 1; the waiter's acquire loads with s_sleep between them):
     //   flag       posted by                waited for by                guards
@@ -1039,12 +1040,16 @@ struct Trio26RecoverLds : Trio26Lds {
     //              wave 3 (j = 3, 4, 7)     (j = 7 .. 2), wave 3 (j = 1) tabphx[j], until entry j replaces it
     //   spost[5+p] wave 2 p + 1             wave 2 p, in phase D         xg[p] (pair p's chain-1 point)
     //   hpost[j]   the j-th summing helper  the j + 1-th                 pt[j] (the comb partials so far)
-    // The last summing helper leaves the G part in pt[3]; that and every other read of a helper's results (the
-    // root helper's sq, rflag, yok among them: K = Zc^2 w comes with the table) lie behind phase D's first
-    // barrier, which the helpers join after their last store.  The rule: no wave
+    //   hpost[kTrioLastSum] the last summing helper  waves 0..3, in phase D      pt[3] (the G part)
+    //   dpost[0]   the root's helper        waves 1, 3, in phase D       sq, rflag, yok (the root and its verdicts)
+    //   dpost[1+p] wave 2 p                 wave 2 p + 1, in phase D     xg[p] (pair p's sum S)
+    // Phase D's first barrier is gone (see there): every result of a helper is read behind its flag, or behind
+    // phase D's second barrier, which the helpers join after their last store (K = Zc^2 w comes with the
+    // table).  The rule: no wave
     // waits for a flag whose poster can be parked at a barrier that needs the waiter.  Every poster above
     // posts before its first barrier after the start, and waits before that only for flags higher in this
-    // table (wave 0 and helper 3 for none).  The table's flags (spost[1], [3], [4], [7] .. [15]) are
+    // table (wave 0 and helper 3 for none; wave 2 p for spost[5+p], which wave 2 p + 1 posts before it
+    // waits).  The table's flags (spost[1], [3], [4], [7] .. [15]) are
     // trio_table_shared's (ec26_trio.h, which orders them and shows that no wait of them has a cycle); the three
     // table waves wait for nothing else before they post.
     // The chain points cannot reuse the table's LDS: xg holds them ([pair] chain point / sum S / X3 Y3); before
@@ -1052,6 +1057,7 @@ struct Trio26RecoverLds : Trio26Lds {
     // canonical limbs, from wave 2 to phase D.
     uint32_t spost[kTfSlots];
     uint32_t hpost[4];
+    uint32_t dpost[3];
     uint32_t xg[2][kTrioWords][64];
     uint32_t tsuf[6][10][64];
     uint32_t kw[10][64];
@@ -1374,6 +1380,16 @@ constexpr CombShare trio_recover_share() {
     return {{{0, a}, {a, b}, {c, 16}, {b, c}}, {{0, 2 * a}, {2 * a, 2 * b}, {2 * c, 32}, {2 * b, 2 * c}}};
 }
 constexpr CombShare kTrioRecoverShare = trio_recover_share();  // [helper]
+// the place in the summing order that stores the G part (helper 2's only if it has windows of its own)
+constexpr int kTrioLastSum = kTrioSplitWin[2] < 16 ? 3 : 2;
+// Which helper a wave 4 .. 7 is.  Wave 4 + j shares SIMD j with chain wave j.  The root's helper (2) is the last
+// to finish by far, and what it shares its SIMD with after phase C decides when: beside a chain-0 wave it
+// competes with that wave's Z^-1 for 52k cycles, beside a chain-1 wave (1 or 3), which is done after one
+// addition and then waits for the root itself, it has the SIMD alone.  So helper 2 runs on wave 7 and helper 3
+// (the digest and its comb windows, finished long before phase C ends) on wave 6.
+constexpr int trio_helper_of_wave(int wave) { return wave == 6 ? 3 : wave == 7 ? 2 : wave - 4; }
+constexpr int kTrioRootWave = 7;
+static_assert(trio_helper_of_wave(kTrioRootWave) == 2, "the root's helper");
 // Known-key verify: 6 / 4 / 5 / 1 to waves 0 / 3 / 2 / 1 (wave 1 builds the table first; wave 3 also adds wave
 // 0's partial), 11 / 8 / 11 / 2 on the 8-bit comb.
 constexpr CombShare kTrioVerifyShare = {{{0, 6}, {15, 16}, {10, 15}, {6, 10}}, {{0, 11}, {30, 32}, {19, 30}, {11, 19}}};
@@ -1591,7 +1607,7 @@ __device__ __forceinline__ void lds_flag_wait_idle(uint32_t* f) {
     while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) __builtin_amdgcn_s_sleep(8);
 }
 
-// What helper h = wave - 4 of tx_verify_trio26_kernel does, one lane per tx, before it joins phase D's
+// What helper h (trio_helper_of_wave) of tx_verify_trio26_kernel does, one lane per tx, before it joins phase D's
 // barriers: helper 2 the square root y = w^((p+1)/4) (fe26_sqrt_cand end to end, the verdict y^2 = w, v's
 // parity) into L.sq / L.rflag / L.yok, helper 3 the digest mod n into L.xe; then every helper with comb
 // windows (kTrioRecoverShare) takes u1 = -e / r with wave 0's r^-1 and its windows of u1 G, and the helpers
@@ -1601,8 +1617,7 @@ template <class IO>
 __device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const IO& io, uint64_t i, bool active, bool ok,
                                                     const fe& r, uint32_t v, const uint32_t* __restrict__ tab, int tab_bits,
                                                     int h, int lane) {
-    constexpr bool kRootAdds = kTrioSplitWin[2] < 16;
-    constexpr int kLast = kRootAdds ? 3 : 2;  // the place in the summing order that stores the G part
+    constexpr int kLast = kTrioLastSum;
     if (h == 2) {
         fe26 X, w, y, ny, t;
         const bool okr = recover_w(X, w, r, v, ok);
@@ -1620,6 +1635,7 @@ __device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const I
         }
         L.rflag[lane] = okr ? 2u : 0u;
         L.yok[lane] = on ? 1u : 0u;
+        lds_flag_post(&L.dpost[0]);
         COOP_T(6);
     } else if (h == 3) {
         fe e;
@@ -1652,7 +1668,7 @@ __device__ __forceinline__ void trio_recover_helper(Trio26RecoverLds& L, const I
         } else {
             coop26_store_jac(L.pt[0], G, lane);
         }
-        if (j != kLast) lds_flag_post(&L.hpost[j]);
+        lds_flag_post(&L.hpost[j]);  // (the last one's is phase D's: the G part)
         COOP_T(10);
     }
 }
@@ -1726,6 +1742,8 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         for (int q = 0; q < kTfSlots; ++q) L.spost[q] = 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) L.hpost[q] = 0u;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) L.dpost[q] = 0u;
     }
     __syncthreads();
     const TrioLane T(lane);
@@ -1741,9 +1759,9 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         bool ok = false;
         fe_zero(r);
         fe_zero(s);
-        if (wave != 0 && active && (wave <= 3 || wave == 4 + 2)) ok = io.rsv(i, r, s, v);
+        if (wave != 0 && active && (wave <= 3 || wave == kTrioRootWave)) ok = io.rsv(i, r, s, v);
         if (helper) {
-            trio_recover_helper(L, io, i, active, ok, r, v, tab, tab_bits, wave - 4, lane);
+            trio_recover_helper(L, io, i, active, ok, r, v, tab, tab_bits, trio_helper_of_wave(wave), lane);
             COOP_T(1);
         } else {
             if (wave == 0) {
@@ -1844,14 +1862,26 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         trio_load(P1, xbuf, lane);
         trio_add(acc, acc, P1, T);
         trio_store(xbuf, acc, lane);
+        lds_flag_post(&L.dpost[1 + (wave >> 1)]);
         fe26 K;
         load_k(K);
         trio_scale_xz(SE, acc, K, T);
     }
-    __syncthreads();  // every wave is past phase C and every helper past its last store; S and T are in LDS
-    const uint32_t rfl = L.rflag[tl];
+    // No barrier here: it made every chain wave wait for the root, which only chain 1 reads, and late.  What was
+    // written before it and is read after it, and the flag that orders each now:
+    //   xg[p] as S (wave 2 p)            read by wave 2 p + 1 below           dpost[1 + p]
+    //   pt[3], the G part (helper 3)     read by waves 0..3 (load_g)          hpost[kTrioLastSum]
+    //   sq (helper 2)                    read by waves 1, 3 for l = Zc y      dpost[0], waited for at the load
+    //   rflag, yok (helper 2)            read by waves 0, 2 for ok2           the second barrier (the loads moved)
+    //   kw, zc (wave 2)                  read by waves 0..3                   spost[3], before phase C
+    //   xg[p] as the chain point         read by wave 2 p above               spost[5 + p]
+    // and the LDS that phase D reuses: xg was the table's prefix products, last read before the table's flags,
+    // which every chain wave has seen before phase C; wave 2 p + 1 overwrites S in xg[p] only after it has loaded
+    // it, and wave 2 p reads xg[p] again behind the second barrier; mbuf (tabphx) is first written behind the
+    // second barrier, which every chain wave reaches after its last table read.
     if (chain == 0) {
         TrioPt G;
+        lds_flag_wait(&L.hpost[kTrioLastSum]);
         load_g(G);
         fe26 Z3;
         trio_add_z(Z3, G, SE, T);
@@ -1868,12 +1898,16 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         fe26_mul(zi3, zi2, zi26);
     } else if (chain == 1) {
         TrioPt S, G;
+        lds_flag_wait(&L.dpost[1 + (wave >> 1)]);
         trio_load(S, xbuf, lane);
+        lds_flag_wait(&L.hpost[kTrioLastSum]);
         load_g(G);
         fe26 y, zc, K, l;
         load_k(K);
         lds_load_fe26(zc, L.zc, tl);
         trio_scale_xz(SE, S, K, T);
+        COOP_T(8);
+        lds_flag_wait(&L.dpost[0]);  // the root, where it is used
 #pragma unroll
         for (int q = 0; q < 10; ++q) y.v[q] = L.sq[q][tl];
         F26_SETM(y, 1);
@@ -1884,11 +1918,11 @@ __device__ __forceinline__ void trio26_recover_body(const IO& io, uint64_t n, co
         trio_store(xbuf, S, lane);
         COOP_T(5);
     }
-    __syncthreads();  // X3, Y3 are in LDS
+    __syncthreads();  // X3, Y3 are in LDS; every wave is past phase C and every helper past its last store
     if (chain == 0) {
         TrioPt O;
         trio_load(O, xbuf, lane);
-        ok2 = (tflags & 1u) != 0u && (rfl & 2u) != 0u && L.yok[tl] != 0u && !O.inf;
+        ok2 = (tflags & 1u) != 0u && (L.rflag[tl] & 2u) != 0u && L.yok[tl] != 0u && !O.inf;
         fe26 X, Y;  // lane 2 holds X3 (Xs), Y3 (S1)
         fe26_mul(X, O.Xs, zi2);
         fe26_mul(Y, O.S1, zi3);

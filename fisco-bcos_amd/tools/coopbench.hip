@@ -80,13 +80,14 @@ int main(int argc, char** argv) {
                 printf(", \"chain_start\": %lld, \"phase_c_end\": %lld, \"phase_c\": %lld, \"phase_d_4\": %lld, "
                        "\"phase_d_5\": %lld",
                        at(w, 9), at(w, 2), at(w, 2) - at(w, 9), at(w, 4), at(w, 5));
-            if (w == 6) printf(", \"root_posted\": %lld", at(w, 6));
-            if (w == 7) printf(", \"digest_posted\": %lld", at(w, 7));
+            if (w == 1 || w == 3) printf(", \"root_wait_reached\": %lld", at(w, 8));
+            if (w == 7) printf(", \"root_posted\": %lld", at(w, 6));
+            if (w == 6) printf(", \"digest_posted\": %lld", at(w, 7));
             if (w >= 4) printf(", \"last_result_posted\": %lld", at(w, 10));
             printf(", \"kernel_end\": %lld}", at(w, 3));
         }
-        printf("}, \"probes\": \"waves 0 / 2: phase_d_4 / 5 = start / end of Z^-1; waves 1 / 3: y loaded / the last "
-               "addition stored\"}\n");
+        printf("}, \"probes\": \"waves 0 / 2: phase_d_4 / 5 = start / end of Z^-1; waves 1 / 3: y loaded (the wait for the root's "
+               "flag, reached at root_wait_reached, is over) / the last addition stored\"}\n");
         return 0;
     }
     printf("{\"cycles_since_start\": {");
